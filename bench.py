@@ -10,14 +10,25 @@ update_parameters (momentum SGD + weight decay, batch = global tile count)
 + zeroing of the gradient accumulators.  Every kernel is HIP (libsrcnn_hip.so
 through its C ABI); inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run measures the headline only: set up, settle + W warmup steps, K
+timed steps, one JSON line (per-kernel figures from hipEvents on sampled timed
+steps ride along).  `--full` adds every other measurement: the wide net, the
+256x256 tile and 4K inference lines, the CPU baselines and, with N > 1, the
+strong-scaling sub-record and the sharded 4K frame (--no-wide, --no-forward,
+--no-cpu-baseline, --no-strong drop single legs of a full run).
+`--dump-outputs DIR` writes what the last timed step left a caller with
+(DIR/params.npy, momentum.npy, grads.npy, float32); the training state is then
+reset to its seeded initial values right before the timed steps, so the dump
+depends on the arguments only, not on how many settle steps the clock took.
 
 `--gpus N > 1` without a torch.distributed.run environment launches the N
 rank processes itself (torch.distributed.run as a child process, before any
 GPU call) and exits with its status; under torch.distributed.run, WORLD_SIZE
-must equal --gpus.  Rank 0 prints ONE JSON line.  With N > 1 the line also
-carries the strong-scaling step (global batch 4096 sharded over the ranks)
+must equal --gpus.  Rank 0 prints ONE JSON line.  With --full and N > 1 the line
+also carries the strong-scaling step (global batch 4096 sharded over the ranks)
 under "strong".  Data is synthetic (smooth random luma patches, seed
 1234 + rank; weights N(0, 1e-3), biases 0).
 """
@@ -726,13 +737,16 @@ def settle(step, settle_ms, sync, world, backend, dev, probe=3):
     return probe + n
 
 
-def timed_region(step, steps, warmup, world, every, stream, S, graph_mode, backend, dev, sync):
+def timed_region(step, steps, warmup, world, every, stream, S, graph_mode, backend, dev, sync,
+                 before_timed=None, after_timed=None):
     """W untimed warmup steps, then K timed steps bracketed by a barrier and a
     device sync on both sides; returns (elapsed max over ranks, profiled
     steps, whether a HIP graph was replayed).  Per-kernel hipEvents on every
     `every`-th step (or on as many extra steps after a graph replay).
     graph_mode (one rank only: a step is then one srcnn_train_step, no
-    collective): the timed steps replay one captured step."""
+    collective): the timed steps replay one captured step.  before_timed():
+    called after the last untimed step, ahead of the opening barrier + sync;
+    after_timed(): called once the clock is read, before any extra step."""
     for _ in range(warmup):
         step()
     sync()
@@ -754,6 +768,8 @@ def timed_region(step, steps, warmup, world, every, stream, S, graph_mode, backe
         if graph is not None:
             graph.launch()  # one untimed replay
             sync()
+    if before_timed is not None:
+        before_timed()
     if world > 1:
         dist.barrier()
     sync()
@@ -774,6 +790,8 @@ def timed_region(step, steps, warmup, world, every, stream, S, graph_mode, backe
         dist.barrier()
     elapsed = time.perf_counter() - t0
     S.profile_enable(False)
+    if after_timed is not None:
+        after_timed()
     if graph is not None:
         n_prof = max(1, steps // every)
         S.profile_enable(True)
@@ -808,9 +826,17 @@ def parse_args(argv=None):
                     help="strong scaling: this many tiles per step in total, sharded over the "
                          "ranks (parallel.shard; SURVEY.md 8(d) config 3: 4096)")
     ap.add_argument("--path", choices=["auto", "generic"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-forward", action="store_true", help="skip the 4K inference line")
-    ap.add_argument("--no-wide", action="store_true", help="skip the wide-net training line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the wide net, the 256x256 "
+                         "tile and 4K inference, the CPU baselines, N > 1: the strong-scaling "
+                         "sub-record and the sharded 4K frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (params, momentum, grads) as "
+                         "DIR/<name>.npy (float32); the state is reset to its seeded initial "
+                         "values right before the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-forward", action="store_true", help="--full: skip the 4K inference line")
+    ap.add_argument("--no-wide", action="store_true", help="--full: skip the wide-net training line")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--profile-every", type=int, default=5,
                     help="per-kernel hipEvents on every N-th timed step (1 = every step)")
@@ -829,7 +855,7 @@ def parse_args(argv=None):
     # ping-pong parameter buffers on the host, so they are always direct calls
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto")
     ap.add_argument("--no-strong", action="store_true",
-                    help="N > 1: skip the strong-scaling sub-record (global batch 4096)")
+                    help="--full, N > 1: skip the strong-scaling sub-record (global batch 4096)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default=None,
                     help="process-group backend (default: gloo with --comm srcnn, nccl with torch)")
     # rehearsal of the N>1 path on a single-GPU box (NOT a measurement):
@@ -897,9 +923,9 @@ def run(args, S, parallel, rank, world, local, device=None):
         global_tiles = B * world
     w, h = TILE, TILE
     P = S.net_param_count(net)
-    # the strong-scaling sub-record (N > 1) reuses the first tiles of this
-    # rank's batch, so allocate for the larger of the two shards
-    Bs = parallel.shard(STRONG_GLOBAL_BATCH, rank, world)[1] if world > 1 else 0
+    # the strong-scaling sub-record (--full, N > 1) reuses the first tiles of
+    # this rank's batch, so allocate for the larger of the two shards
+    Bs = parallel.shard(STRONG_GLOBAL_BATCH, rank, world)[1] if world > 1 and args.full else 0
     Bmax = max(B, Bs, 1)
     rng = np.random.default_rng(1234 + rank)
     X, T = synthetic_batch(rng, Bmax, w, h)
@@ -970,8 +996,9 @@ def run(args, S, parallel, rank, world, local, device=None):
             S.train_step(net, Xd, Td, w, h, B, params, grads, mom, mu, wd, lr, global_tiles,
                          None, ws, ws_bytes, stream)
 
-    # The single-GPU side lines (the wide net, one 256x256 tile, 4K inference)
-    # are measured before the headline.  Order and pause matter on this part
+    # --full: the single-GPU side lines (the wide net, one 256x256 tile, 4K
+    # inference) are measured before the headline; a plain run goes straight
+    # to the headline's settle() steps.  Order and pause matter on this part
     # (tools/first_step.py): right after ~0.15 s of the
     # wide net's full-power load the GPU stalls the next launch for 8-24 ms
     # (a power-state transition; a 0.2 s idle pause avoids it), and a step
@@ -985,11 +1012,11 @@ def run(args, S, parallel, rank, world, local, device=None):
     # that to N); only N = 1 reports these lines.
     S.preload(net)
     side = {}
-    if not args.no_wide:
+    if args.full and not args.no_wide:
         side["wide"] = wide_training(S)
         sync()
         time.sleep(0.5)
-    if not args.no_forward:
+    if args.full and not args.no_forward:
         side["forward_tile_256"] = forward_tile_256(S, net_t)
         side["forward"] = forward_4k(S, net_t)
     if world > 1:
@@ -1005,19 +1032,44 @@ def run(args, S, parallel, rank, world, local, device=None):
     # every launch cost 2.5% of the step even as fence-free timing events
     # (1.011 vs 0.986 ms, same box), so the sampled steps carry the
     # instrumentation and the others run bare.
+    reset_state = None
+    if args.dump_outputs:
+        # the settle step count follows the clock, so the state the timed
+        # steps start from is put back to the seeded initial one: the dump then
+        # depends on the arguments alone (a lazy step's owed update is applied
+        # first, so that nothing of the untimed steps is left pending)
+        prm0 = torch.from_numpy(prm.copy())
+
+        def reset_state():
+            finish(step)
+            bufs["p"].copy_(prm0)
+            bufs["m"].zero_()
+            grads.zero_()
+
+    dump = {}
+
+    def snapshot():
+        """what a caller of the step holds after the last timed step"""
+        sync()
+        for k, v in (("params", bufs["p"]), ("momentum", bufs["m"]), ("grads", grads)):
+            dump[k] = v.detach().cpu().numpy().astype(np.float32, copy=True)
+
     n_settle = settle(step, args.settle_ms, sync, world, backend, dev)
-    elapsed, n_prof, used_graph = timed_region(step, args.steps, args.warmup, world, every, stream, S,
-                                               graph_mode, backend, dev, sync)
+    elapsed, n_prof, used_graph = timed_region(
+        step, args.steps, args.warmup, world, every, stream, S, graph_mode, backend, dev, sync,
+        before_timed=reset_state, after_timed=snapshot if args.dump_outputs and not lazy else None)
     _mark("headline timed steps done")
     kernel_path = S.last_path()
     split = split_profiled(S)  # (the step's own kernels: read before the side legs run)
     stats = S.profile_stats()
     finish(step)
+    if args.dump_outputs and lazy:
+        snapshot()  # (a lazy step's last update is applied by finish())
 
-    # N > 1: the strong-scaling step in the same run (global batch 4096
+    # --full, N > 1: the strong-scaling step in the same run (global batch 4096
     # sharded over the ranks: 512 tiles per rank at N = 8), timed the same way
     strong_rec = None
-    if world > 1 and not strong and not args.no_strong:
+    if args.full and world > 1 and not strong and not args.no_strong:
         sstep = dp_step(Bs, STRONG_GLOBAL_BATCH)
         s_settle = settle(sstep, args.settle_ms, sync, world, backend, dev)
         s_el, s_prof, s_graph = timed_region(sstep, args.steps, args.warmup, world, every, stream, S,
@@ -1036,7 +1088,7 @@ def run(args, S, parallel, rank, world, local, device=None):
         _mark("strong timed steps done")
     assert np.isfinite(bufs["p"].cpu().numpy()).all(), "non-finite parameters after training"
     fwd_sharded = None
-    if world > 1 and not args.no_forward:
+    if args.full and world > 1 and not args.no_forward:
         def reduce_max(v):
             t = torch.tensor([v], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1126,9 +1178,14 @@ def run(args, S, parallel, rank, world, local, device=None):
         if fwd_sharded is not None:
             out["forward"] = fwd_sharded
         out.update(side)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(net_t, budget_s=args.cpu_budget)
             out["cpu_forward_baseline"] = cpu_forward_baseline(net_t)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            out["outputs"] = sorted(dump)
         print(json.dumps(out), flush=True)
     if comm is not None:
         comm.close()

@@ -209,7 +209,7 @@ def _run_ranks(tmp_path, argv, world=2, stub_kw=None, timeout=150):
     return [p.exitcode for p in procs], logs, outs, errs, time.time() - t0
 
 
-BASE = ["--gpus", "2", "--no-wide", "--no-forward", "--no-cpu-baseline", "--batch", "8"]
+BASE = ["--gpus", "2", "--full", "--no-wide","--no-forward", "--no-cpu-baseline", "--batch", "8"]
 
 
 def _collectives(log):

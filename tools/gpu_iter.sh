@@ -15,7 +15,7 @@ else
 fi
 rc=$?; echo "pytest rc=$rc"; tail -4 "$OUT/pytest.log"
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py ${BENCH_ARGS:---no-cpu-baseline} > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline} > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.err"
 [ $rc -eq 0 ] || exit $rc
 python3 - "$OUT/bench.json" <<'PY'

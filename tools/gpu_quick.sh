@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-q}; mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1
 rc=$?; echo "pytest rc=$rc"; tail -4 "$OUT/pytest.log"
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.err"
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys

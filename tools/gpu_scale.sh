@@ -17,7 +17,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -5 "$OUT/pytest_gpu.log"
   ok $rc || exit $rc
 fi
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; head -c 1500 "$OUT/bench.json"; echo; tail -3 "$OUT/bench.err"
 [ $rc -eq 0 ] || exit $rc
 for gb in 512 1024 2048 4096; do

@@ -17,7 +17,7 @@ run_pass() {
   [ ${#list[@]} -eq 0 ] && { echo "pass $name: no counters available"; return 0; }
   echo "pass $name: ${list[*]}"
   timeout -k 10 300 rocprofv3 --pmc "${list[@]}" --kernel-trace --output-format csv -d "$OUT/$name" -o run \
-    -- python3 "$ROOT/bench.py" --steps ${PMC_STEPS:-3} --warmup 1 --no-cpu-baseline ${PMC_BENCH_ARGS:-} > "$OUT/$name.log" 2>&1
+    -- python3 "$ROOT/bench.py" --full --steps ${PMC_STEPS:-3} --warmup 1 --no-cpu-baseline ${PMC_BENCH_ARGS:-} > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "pass $name rc=$rc"
   return $rc

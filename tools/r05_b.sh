@@ -27,7 +27,7 @@ for rep in 1 2; do
   for v in head cur; do
     lib=cnn-super-resolution_amd/lib/variants/libsrcnn_hip_head.so
     [ $v = cur ] && lib=cnn-super-resolution_amd/lib/libsrcnn_hip.so
-    SRCNN_HIP_LIB=$ROOT/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-wide --steps 20 --warmup 5 \
+    SRCNN_HIP_LIB=$ROOT/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-wide --steps 20 --warmup 5 \
       > "$OUT/fwd_${v}_$rep.json" 2> "$OUT/fwd_${v}_$rep.err" || exit $?
     python3 -c "import json; d=json.load(open('$OUT/fwd_${v}_$rep.json')); f=d['forward']; print('$v', $rep, 'frame', f['ms_per_frame'], {k: v['ms_per_frame'] for k, v in f['kernels'].items()}, 'step', d['ms_per_step'])"
   done

@@ -20,11 +20,11 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
 fi
 summ() { python3 -c "import json; d=json.load(open('$1')); print('$2', d['value'], d['ms_per_step'], d['config'].get('settle_steps'), {k: v['ms_per_step'] for k, v in d['kernels'].items()})"; }
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/d20a.json" 2> "$OUT/d20a.err" || exit $?
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/d20a.json" 2> "$OUT/d20a.err" || exit $?
 summ "$OUT/d20a.json" d20a
-timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/d100.json" 2> "$OUT/d100.err" || exit $?
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/d100.json" 2> "$OUT/d100.err" || exit $?
 summ "$OUT/d100.json" d100
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20b.json" 2> "$OUT/d20b.err" || exit $?
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20b.json" 2> "$OUT/d20b.err" || exit $?
 summ "$OUT/d20b.json" d20b
 timeout -k 10 300 python tools/strong_shard.py > "$OUT/strong.jsonl" 2> "$OUT/strong.err" || exit $?
 cat "$OUT/strong.jsonl"

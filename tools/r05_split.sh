@@ -18,5 +18,5 @@ for b in 512 1024; do
   SRCNN_L3R_SPLIT_BELOW=0 timeout -k 10 300 python tools/strong_shard.py --batch $b --modes ${MODES:-lazy,step} > "$OUT/whole_$b.jsonl" 2> "$OUT/whole_$b.err" || exit $?
   echo "whole b=$b"; cat "$OUT/whole_$b.jsonl"
 done
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20.json" 2> "$OUT/d20.err" || exit $?
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20.json" 2> "$OUT/d20.err" || exit $?
 python3 -c "import json; d=json.load(open('$OUT/d20.json')); print('d20', d['value'], d['ms_per_step'], {k: v['ms_per_step'] for k, v in d['kernels'].items()})"

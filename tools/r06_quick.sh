@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest $TESTS -q -x --timeout 120 --timeout-metho
 rc=$?; echo "pytest rc=$rc"; tail -15 "$OUT/pytest.log"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 if [ -z "${NO_BENCH:-}" ]; then
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:---no-cpu-baseline} > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline} > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.err"
   python3 - "$OUT/bench.json" <<'PY'
 import json,sys

@@ -21,16 +21,16 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
 fi
 summ() { python3 -c "import json; d=json.load(open('$1')); print('$2', d['value'], d['ms_per_step'], 'wide', d.get('wide', {}).get('ms_per_step'), {k: v['ms_per_step'] for k, v in d['kernels'].items()})"; }
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/d20a.json" 2> "$OUT/d20a.err" || exit $?
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/d20a.json" 2> "$OUT/d20a.err" || exit $?
 summ "$OUT/d20a.json" d20a
-timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/d100.json" 2> "$OUT/d100.err" || exit $?
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/d100.json" 2> "$OUT/d100.err" || exit $?
 summ "$OUT/d100.json" d100
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20b.json" 2> "$OUT/d20b.err" || exit $?
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/d20b.json" 2> "$OUT/d20b.err" || exit $?
 summ "$OUT/d20b.json" d20b
 timeout -k 10 300 python tools/strong_shard.py > "$OUT/strong.jsonl" 2> "$OUT/strong.err" || exit $?
 grep mode "$OUT/strong.jsonl"
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/rocprof_bench" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$ROOT/$OUT/rocprof_d20.log" 2>&1 || exit $?
+  python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$ROOT/$OUT/rocprof_d20.log" 2>&1 || exit $?
 cd "$ROOT" && f=$(find "$OUT/rocprof_bench" -name '*kernel_stats.csv' | head -1) && [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv"
 cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/rocprof_strong" -o run --output-format csv -- \
   python3 "$ROOT/tools/strong_shard.py" --modes lazy,separate > "$ROOT/$OUT/rocprof_strong.log" 2>&1 || exit $?

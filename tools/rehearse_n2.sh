@@ -7,7 +7,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:-rehearse}; mkdir -p "$OUT"
-timeout -k 10 300 python bench.py --gpus 2 --steps 10 --warmup 3 --comm torch --dist-backend gloo \
+timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --warmup 3 --comm torch --dist-backend gloo \
   --all-ranks-on-device 0 --no-wide > "$OUT/n2.json" 2> "$OUT/n2.err"
 rc=$?; echo "n2 rc=$rc"; tail -1 "$OUT/n2.json"
 [ $rc -eq 0 ] || exit $rc
