@@ -101,8 +101,22 @@ inline bool d1x6_fits(int w, int h, bool d3 = false) {
   return w <= 57 && D6Lds(w, h, rg, d3).bytes <= 160 * 1024 && (!d3 || rg.nch >= 4);
 }
 
-// the all-zero delta2 row that dummy slots load (runs.hpp: slots past the tile)
-__device__ float g_d6_zero[32] = {};
+// the all-zero delta2 row that dummy slots load (runs.hpp: slots past the
+// tile), with the lane-half offset and the four 16-B quads of a real row
+constexpr int kD6Zero = 32;
+__device__ __attribute__((aligned(16))) float g_d6_zero[kD6Zero] = {};
+// ld_d2's addressing: a row's lane-half offset (kD3: A2 rows in crow order,
+// n = 4h + 8k ..; else delta2 rows, n = 8h + 16 (k >> 1) + 4 (k & 1) ..) and
+// its 16-B quad k.  The zero row takes the same offsets as a real row.
+constexpr int d6_row_half(bool d3, int h) { return (d3 ? 4 : 8) * h; }
+constexpr int d6_zero_half(bool d3, int h) { return d6_row_half(d3, h); }
+constexpr int d6_row_quad(bool d3, int k) { return d3 ? 8 * k : 16 * (k >> 1) + 4 * (k & 1); }
+constexpr bool d6_zero_row_covers(bool d3) {
+  for (int h = 0; h < 2; h++)
+    for (int k = 0; k < 4; k++)
+      if (d6_zero_half(d3, h) + d6_row_quad(d3, k) + 4 > kD6Zero) return false;
+  return true;
+}
 
 // c0 += a0 . b0 and c1 += a1 . b1 (two x6 chains interleaved, so no MFMA
 // waits on its predecessor's result)
@@ -326,11 +340,12 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   auto ld_d2 = [&](int j, int c) {
     const int pix = slots[c * 32 + li];
     const float* src = kD3 ? A2 : D2;
-    const float* d2 =
-        pix >= 0 ? src + ((size_t)item_sample(j) * npx + pix) * N2 + (kD3 ? 4 : 8) * h : g_d6_zero + 8 * h;
+    // every 16-B load of a dummy slot lies inside the zero row, in both modes
+    static_assert(d6_zero_row_covers(false) && d6_zero_row_covers(true), "dummy-slot loads past g_d6_zero");
+    const float* d2 = pix >= 0 ? src + ((size_t)item_sample(j) * npx + pix) * N2 + d6_row_half(kD3, h)
+                               : g_d6_zero + d6_zero_half(kD3, h);
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-      d2r[k] = *reinterpret_cast<const f32x4*>(d2 + (kD3 ? 8 * k : 16 * (k >> 1) + 4 * (k & 1)));
+    for (int k = 0; k < 4; k++) d2r[k] = *reinterpret_cast<const f32x4*>(d2 + d6_row_quad(kD3, k));
   };
   auto ld_a1 = [&](int j, int c, int k0 = 0, int k1 = 8) __attribute__((always_inline)) {
     const float* a1 = A1T + ((size_t)item_sample(j) * nch + c) * (64 * 32) + li * 32 + 4 * h;

@@ -141,11 +141,13 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
   // kD3Out: Q in split-bf16 products on v_mfma_f32_16x16x32_bf16 (one
   // k-step over the 32 channels): its B operand W3 as a split image, lane
   // (tap 16t + lq, lg), element j <-> channel chan(j, lg) = 4lg + j (j < 4),
-  // 16 + 4lg + j - 4, in the space of the fp32 images (not used then)
+  // 16 + 4lg + j - 4, in the space of the fp32 images (not used then).  Only
+  // the TT tap tiles that Q reads are written: a second tile at f3 <= 4 would
+  // run past the fp32 images of that F3 into the delta3 grid.
   __bf16* const w3q = reinterpret_cast<__bf16*>(w3s);
-  static_assert(2 * 3 * 512 * 2 <= (25 * kL3RW3S + 32 * kL3RWdS) * 4, "split Q image in the fp32 images' space");
+  static_assert(TT * 3 * 512 * 2 <= (K3 * kL3RW3S + 32 * kL3RWdS) * 4, "split Q image in the fp32 images' space");
   if constexpr (kD3Out) {
-    for (int e = tid; e < 2 * 64 * 8; e += kL3RThreads) {
+    for (int e = tid; e < TT * 64 * 8; e += kL3RThreads) {
       const int j = e & 7, L_ = (e >> 3) & 63, t = e >> 9, lq_ = L_ & 15, lg_ = L_ >> 4;
       const int ch = j < 4 ? 4 * lg_ + j : 16 + 4 * lg_ + j - 4, tq = 16 * t + lq_;
       __bf16 p[3];

@@ -198,7 +198,23 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  * last-layer delta, deltas and gradients (:243-323).  Gradients are
  * ACCUMULATED into `grads` (flat layout).  X = mean-subtracted input luma,
  * T = ground-truth luma, both [batch][h][w].  If sq_err != NULL the chunk's
- * squared error (validation metric) is ADDED to *sq_err (device). */
+ * squared error (validation metric) is ADDED to *sq_err (device).
+ *
+ * Memory contract of every call that takes a workspace (the net-level calls
+ * here and below, srcnn_conv_grad_acc and the reductions):
+ *   - `ws` is ws_bytes >= the matching *_workspace_bytes() of device memory
+ *     (exactly that many suffice) and needs NO initialisation: the call reads nothing of
+ *     `ws` that a kernel of the same call has not written before (its previous
+ *     contents -- zeros, NaN, anything -- never reach a result);
+ *   - the call writes nothing outside [ws, ws + ws_bytes) and the documented
+ *     extent of its outputs (grads: srcnn_net_param_count floats; sq_err: one
+ *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
+ *     A3 extent; srcnn_train_activations: the three extents it documents);
+ *   - buffers the call only reads (X, T, params) are not written, and nothing
+ *     outside their extent reaches a result.
+ * The results are bit-identical whatever `ws` held before and whatever lies
+ * around the buffers (tests/test_memory_hygiene_gpu.py pins this with
+ * exact-size poisoned workspaces and guard bands). */
 SRCNN_API size_t srcnn_train_workspace_bytes(const srcnn_net* net, uint32_t w,
                                              uint32_t h, uint32_t batch);
 SRCNN_API int srcnn_train_fwd_bwd(const srcnn_net* net, const float* X,
@@ -217,7 +233,11 @@ SRCNN_API int srcnn_update_all(const srcnn_net* net, float* params,
                                uint32_t batch, srcnn_stream_t stream);
 
 /* Forward / inference (src/ConfigBasedDataPipeline.cpp:114-126, :200-241):
- * out = A3 [batch][h-pad][w-pad], pad = f1+f2+f3-3. */
+ * out = A3 [batch][h-pad][w-pad], pad = f1+f2+f3-3.  The memory contract at
+ * srcnn_train_workspace_bytes holds here too: `ws` (srcnn_forward_workspace_bytes
+ * bytes suffice) needs no initialisation, the call reads nothing of it that it
+ * did not write itself, and it writes only inside `ws` and the
+ * batch x (h-pad) x (w-pad) floats of `out`, every one of which it writes. */
 SRCNN_API size_t srcnn_forward_workspace_bytes(const srcnn_net* net,
                                                uint32_t w, uint32_t h,
                                                uint32_t batch);

@@ -73,6 +73,80 @@ def host(t, torch):
     return t.detach().cpu().numpy()
 
 
+# Guard bands (tests/test_memory_hygiene_gpu.py): GUARD_FLOATS floats in front
+# of and behind a buffer, both inside one torch allocation, so a stray store
+# lands in memory the test owns and can inspect.  A multiple of 64 floats (the
+# view keeps torch's 256-B alignment); 1024 floats hold a whole stray 128-B
+# row or 4 KB slab row.  The two poison values: NaN, which any arithmetic
+# keeps, and +1e30, which a leaked `> 0` ReLU mask lets through (NaN > 0 is
+# false, so NaN alone hides a mask read from foreign memory).
+GUARD_FLOATS = 1024
+POISONS = (float("nan"), 1e30)
+_GUARDS = {}  # id(view) -> (view, base, guard floats, fill bit pattern)
+
+
+def fill_bits(fill):
+    """The int32 bit pattern of float32(fill)."""
+    return int(np.array([fill], np.float32).view(np.int32)[0])
+
+
+def guarded(a, fill, inner=None, guard=GUARD_FLOATS):
+    """A float32 device view holding `a` (a numpy array, a torch tensor, or an
+    element count for an uninitialised buffer) with `guard` floats of `fill`
+    in front of it and behind it, all carved from one torch allocation.  An
+    element count gives a buffer filled with `inner` (default: `fill`), e.g. a
+    poisoned workspace of exactly n floats.  guards_intact(view) later
+    checks both bands."""
+    import torch
+    assert guard >= 1024 and guard % 64 == 0, guard
+    if isinstance(a, (int, np.integer)):
+        n, src = int(a), None
+    elif isinstance(a, np.ndarray):
+        src = torch.from_numpy(np.array(a, dtype=np.float32).ravel())  # (a copy: `a` may be read-only)
+        n = src.numel()
+    else:
+        src = a.detach().reshape(-1)
+        assert src.dtype == torch.float32, src.dtype
+        n = src.numel()
+    base = torch.empty(n + 2 * guard, dtype=torch.float32, device="cuda")
+    base.view(torch.int32).fill_(fill_bits(fill))
+    view = base[guard:guard + n]
+    if src is not None:
+        view.copy_(src)
+    elif inner is not None:
+        view.view(torch.int32).fill_(fill_bits(inner))
+    assert view.data_ptr() == base.data_ptr() + 4 * guard and view.data_ptr() % 256 == 0
+    _GUARDS[id(view)] = (view, base, guard, fill_bits(fill))
+    return view
+
+
+def guards_intact(*views):
+    """True if both guard bands of every guarded() view still hold their fill,
+    bit for bit (compared as int32); else raises AssertionError naming the
+    view's position, the band and the first changed offsets.  The views are
+    forgotten afterwards."""
+    import torch
+    torch.cuda.synchronize()
+    for k, v in enumerate(views):
+        view, base, guard, bits = _GUARDS.pop(id(v))
+        assert view is v
+        ints = base.view(torch.int32)
+        for band, sl in (("front", ints[:guard]), ("back", ints[guard + v.numel():])):
+            bad = (sl != bits).nonzero().flatten()
+            assert bad.numel() == 0, ("guard band overwritten: buffer %d (%d floats), %s band, %d floats changed, "
+                                      "first at band offsets %s" % (k, v.numel(), band, bad.numel(),
+                                                                    bad[:8].tolist()))
+    return True
+
+
+def same_bits(a, b):
+    """Bit-for-bit equality of two float32 arrays (NaN payloads and signed
+    zeros included)."""
+    a = np.ascontiguousarray(a, np.float32)
+    b = np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
 def max_rel_err(got, ref):
     got = np.asarray(got, np.float64).ravel()
     ref = np.asarray(ref, np.float64).ravel()
