@@ -72,6 +72,28 @@ int net_dims(const srcnn_net* net, uint32_t w, uint32_t h, NetDims* d) {
 
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
+// srcnn_upscale_*: the sizes of one upscale, checked against what the kernels
+// of upscale.hip can index (int coordinates and element offsets below 2^31)
+struct UpDims {
+  uint32_t W, H, PW, PH;  // output image, padded plane
+};
+int up_dims(const char* who, uint32_t w, uint32_t h, uint32_t scale, uint32_t pad, UpDims* d) {
+  SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
+  SRCNN_REQUIRE(w > 0 && h > 0, "%s: empty image %ux%u", who, w, h);
+  const uint64_t lim = 0x7fffffffull;  // INT32_MAX
+  const uint64_t W = (uint64_t)w * scale, H = (uint64_t)h * scale;
+  SRCNN_REQUIRE(W + pad <= lim && H + pad <= lim && (W + pad) * (H + pad) <= lim &&
+                    3 * W * H <= lim,
+                "%s: %ux%u x%u with padding %u exceeds the kernels' 32-bit index: the padded plane's "
+                "floats and the rgb bytes must each number at most 2^31-1",
+                who, w, h, scale, pad);
+  d->W = (uint32_t)W;
+  d->H = (uint32_t)H;
+  d->PW = (uint32_t)(W + pad);
+  d->PH = (uint32_t)(H + pad);
+  return SRCNN_OK;
+}
+
 size_t grad_ws_bytes(uint32_t n_prev, uint32_t n_cur, uint32_t f, uint32_t ow, uint32_t oh,
                      uint32_t batch) {
   size_t b = 0;
@@ -232,6 +254,22 @@ int srcnn_swap_luma(const uint8_t* rgba, const float* new_luma, uint8_t* rgb, ui
   return srcnn::swap_luma(rgba, new_luma, rgb, w, h, luma_w, luma_h, as_stream(stream));
 }
 
+int srcnn_upscale_luma(const uint8_t* rgba, float* luma_padded, uint32_t w, uint32_t h,
+                       uint32_t scale, uint32_t pad, srcnn_stream_t stream) {
+  UpDims d;
+  if (int rc = up_dims("upscale_luma", w, h, scale, pad, &d)) return rc;
+  SRCNN_REQUIRE(rgba && luma_padded, "upscale_luma: null buffer");
+  return srcnn::upscale_luma(rgba, luma_padded, w, h, scale, pad, as_stream(stream));
+}
+
+int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* rgb, uint32_t w,
+                          uint32_t h, uint32_t scale, srcnn_stream_t stream) {
+  UpDims d;
+  if (int rc = up_dims("upscale_compose", w, h, scale, 0, &d)) return rc;
+  SRCNN_REQUIRE(rgba && new_luma && rgb, "upscale_compose: null buffer");
+  return srcnn::upscale_compose(rgba, new_luma, rgb, w, h, scale, as_stream(stream));
+}
+
 // ---------------------------------------------------------------------------
 // network level
 // ---------------------------------------------------------------------------
@@ -257,7 +295,7 @@ int srcnn_preload(const srcnn_net* net) {
   if (int rc = srcnn_net_offsets(net, off)) return rc;
   int rc;
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
-      (rc = srcnn::wide::preload(net)) < 0)
+      (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0)
     return rc;
   return srcnn::preload_update();
 }
@@ -578,6 +616,65 @@ int srcnn_forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, 
     return rc;
   return seq.done(srcnn_conv_fwd(A2, out, params + off[4], params + off[5], d.w2, d.h2, net->n2, 1,
                                  net->f3, 0, batch, stream));
+}
+
+// regions of the upscale workspace: padded plane | net output | reduction
+// scratch | forward workspace, each 256-byte aligned
+struct UpWs {
+  size_t plane, out, red, fwd, total;  // byte offsets of the regions, and their sum
+  size_t red_bytes, fwd_bytes;         // what the reduction and the forward are given
+};
+static bool up_ws(const srcnn_net* net, const UpDims& d, UpWs* L) {
+  L->fwd_bytes = srcnn_forward_workspace_bytes(net, d.PW, d.PH, 1);
+  if (L->fwd_bytes == 0) return false;
+  const size_t plane = (size_t)d.PW * d.PH;
+  L->red_bytes = srcnn_reduce_workspace_bytes(plane);
+  L->plane = 0;
+  L->out = L->plane + align_up(plane * sizeof(float));
+  L->red = L->out + align_up((size_t)d.W * d.H * sizeof(float));
+  L->fwd = L->red + align_up(L->red_bytes);
+  L->total = L->fwd + align_up(L->fwd_bytes);
+  return true;
+}
+
+size_t srcnn_upscale_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                     uint32_t scale) {
+  size_t off[6];
+  UpDims d;
+  UpWs L;
+  if (srcnn_net_offsets(net, off)) return 0;
+  const uint64_t pad = (uint64_t)net->f1 + net->f2 + net->f3 - 3;
+  if (pad > 0x7fffffffull || up_dims("upscale", w, h, scale, (uint32_t)pad, &d)) return 0;
+  return up_ws(net, d, &L) ? L.total : 0;
+}
+
+int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h,
+                  uint32_t scale, const float* params, uint8_t* rgb, void* ws, size_t ws_bytes,
+                  srcnn_stream_t stream) {
+  SRCNN_REQUIRE(net, "upscale: null srcnn_net");
+  const uint64_t pad64 = (uint64_t)net->f1 + net->f2 + net->f3 - 3;
+  SRCNN_REQUIRE(pad64 <= 0x7fffffffull, "upscale: total padding %llu too large",
+                (unsigned long long)pad64);
+  const uint32_t pad = (uint32_t)pad64;
+  UpDims d;
+  if (int rc = up_dims("upscale", w, h, scale, pad, &d)) return rc;
+  SRCNN_REQUIRE(rgba && params && rgb && ws, "upscale: null buffer");
+  UpWs L;
+  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "upscale: workspace %zu B < %zu B", ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  float* out = reinterpret_cast<float*>(p + L.out);
+  int rc;
+  if ((rc = srcnn_upscale_luma(rgba, plane, w, h, scale, pad, stream))) return rc;
+  // the mean of what the net sees: the whole padded plane; not added back
+  // (the reference flow: cnn.cpp subtracts it and pastes the net's output)
+  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
+    return rc;
+  return srcnn_upscale_compose(rgba, out, rgb, w, h, scale, stream);
 }
 
 }  // extern "C"

@@ -216,5 +216,13 @@ int extract_luma(const uint8_t* rgba, float* luma, uint32_t w, uint32_t h, int n
                  hipStream_t s);
 int swap_luma(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
               uint32_t lw, uint32_t lh, hipStream_t s);
+// upscale.hip: bicubic x scale (1..4) luma into the edge-replicated padded
+// plane [(scale*h+pad)][(scale*w+pad)], and the composition of the bicubic
+// r, g, b with the net's luma [scale*h][scale*w] into rgb
+int upscale_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint32_t scale,
+                 uint32_t pad, hipStream_t s);
+int upscale_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
+                    uint32_t scale, hipStream_t s);
+int preload_upscale();
 
 }  // namespace srcnn

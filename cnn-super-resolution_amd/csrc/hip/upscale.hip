@@ -1,0 +1,319 @@
+// upscale.hip -- the device front and back end of srcnn_upscale:
+//   upscale_luma     rgba [h][w][4] u8 -> bicubic x S luma, edge-replicated into
+//                    the padded plane [(S*h+P)][(S*w+P)] f32 the net reads
+//   upscale_compose  bicubic x S of the source's r, g, b + the net's luma ->
+//                    rgb [S*h][S*w][3] u8 (swap_luma's constants and rounding)
+// The reference has no counterpart (its README: "application input is already
+// scaled image"); the resampling is specified in DESIGN.md 10.1.
+//
+// Both kernels: one workgroup per tile of JX x JY source pixels, i.e.
+// (JX*S) x (JY*S) output pixels (struct Tile).  The source patch the tile's
+// taps reach (j-2 .. j+2: (JX+4) x (JY+4), indices clamped to the image) is
+// fetched once with one 4-byte load per pixel and kept in LDS (luma as floats,
+// colours as the RGBA8 word); the horizontal pass writes JY+4 rows of S*JX
+// values to LDS; the vertical pass reads four of those rows per output into
+// registers.  S is a template parameter: the only divisions left are by that
+// constant, once per output row, and the tile decode once per workgroup.
+#include "common.hpp"
+#include "ops.hpp"
+
+namespace srcnn {
+namespace {
+
+constexpr int kThreads = 256;
+// Tile geometry, by measurement at 1920 x 1080 x2.
+// upscale_luma: 32 x 16 source pixels at every scale (64 x 8 and 64 x 16 at
+// S = 2 were 6 - 8 % slower).  upscale_compose: 64 x 8 at S <= 2, which makes
+// a tile's rgb rows 192 - 384 bytes, so that most of the 128-byte lines a row
+// touches are written whole by one workgroup, and keeps the three channels of
+// the horizontal pass within 25 KB of LDS (32 x 16 was 13 % slower); 32 x 16
+// at S >= 3.
+template <int S, bool COMPOSE>
+struct Tile {
+  static constexpr int JX = COMPOSE && S <= 2 ? 64 : 32, JY = COMPOSE && S <= 2 ? 8 : 16;  // source pixels
+  static constexpr int TX = JX * S, TY = JY * S;                                // output pixels
+  static constexpr int PC = JX + 4, PR = JY + 4;                                // staged patch
+  static constexpr int PCP = PC + 1;                                            // its LDS pitch
+};
+
+// Keys cubic, a = -0.5
+constexpr double keys(double x) {
+  x = x < 0 ? -x : x;
+  return x <= 1 ? (1.5 * x - 2.5) * x * x + 1 : x < 2 ? ((-0.5 * x + 2.5) * x - 4) * x + 2 : 0;
+}
+// phase k of scale s: d = (k+0.5)/s - 0.5, b = floor(d) (-1 or 0), t = d - b;
+// taps j+b-1 .. j+b+2 at distances t+1, t, 1-t, 2-t
+constexpr int tap_base(int s, int k) { return 2 * k + 1 < s ? -1 : 0; }
+struct Weights {
+  float w[5][4][4];  // [scale][phase][tap], computed in double, rounded once
+};
+constexpr Weights make_weights() {
+  Weights t{};
+  for (int s = 1; s <= 4; s++)
+    for (int k = 0; k < s; k++) {
+      const double d = (k + 0.5) / s - 0.5, tt = d - tap_base(s, k);
+      for (int i = 0; i < 4; i++) t.w[s][k][i] = (float)keys(tt + 1 - i);
+    }
+  return t;
+}
+__constant__ Weights c_up = make_weights();
+
+// The two scale-1 anchors are bit-exact: the plane's interior is
+// srcnn_extract_luma's output and the composition srcnn_swap_luma's.  Under
+// -ffp-contract=fast the compiler chooses which of those kernels' products
+// fuse into an fma, and the choice shows in the last bit; these two helpers
+// spell out the operations extract_luma_kernel and swap_luma_kernel
+// (ops_generic.hip) are built from, with contraction off, so that the
+// context they are inlined into cannot change them
+// (tests/test_upscale_gpu.py pins both against the kernels themselves).
+__device__ __forceinline__ float luma_of(float r, float g, float b) {
+#pragma clang fp contract(off)
+  const float v = fmaf(b, 0.114f, r * 0.299f + g * 0.587f);
+  return v / 255.0f;
+}
+__device__ __forceinline__ void compose_px(float r, float g, float b, float nl, uint8_t* q) {
+#pragma clang fp contract(off)
+  const float Cb = fmaf(b, 0.5f, fmaf(r, -0.1687f, g * -0.3312f));
+  const float Cr = fmaf(b, -0.0813f, fmaf(r, 0.5f, g * -0.4186f));
+  // Y = nl * 255 is never rounded on its own: Y + Cb * k is one fma
+  const float R = Cr * 1.4f + fmaf(nl, 255.0f, Cb * 0.0f);
+  const float G = fmaf(nl, 255.0f, Cb * -0.343f) - Cr * 0.711f;
+  const float B = Cr * 0.0f + fmaf(nl, 255.0f, Cb * 1.765f);
+  q[0] = (uint8_t)(unsigned)fminf(fmaxf(R, 0.0f), 255.0f);
+  q[1] = (uint8_t)(unsigned)fminf(fmaxf(G, 0.0f), 255.0f);
+  q[2] = (uint8_t)(unsigned)fminf(fmaxf(B, 0.0f), 255.0f);
+}
+
+// the four weights of phase ky (not a compile-time value in the vertical
+// pass): selected from the S phases' weights, which are uniform scalar loads,
+// instead of a per-lane load from the table
+template <int S>
+__device__ __forceinline__ void phase_weights(int ky, float (&w)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    float v = c_up.w[S][0][i];
+#pragma unroll
+    for (int k = 1; k < S; k++) v = ky == k ? c_up.w[S][k][i] : v;
+    w[i] = v;
+  }
+}
+
+// clamped fetch of the tile's source patch: one uchar4 load per pixel,
+// consecutive lanes consecutive pixels of a row
+template <typename T, typename Store>
+__device__ __forceinline__ void stage_patch(const uint8_t* __restrict__ rgba, int w, int h, int j0,
+                                            int i0, Store store) {
+  constexpr int LW = T::PC <= 64 ? 64 : 128;  // lanes per patch row
+  const int c = threadIdx.x % LW;
+  if (c >= T::PC) return;
+  const int sx = min(max(j0 - 2 + c, 0), w - 1);
+  for (int r = threadIdx.x / LW; r < T::PR; r += kThreads / LW) {
+    const int sy = min(max(i0 - 2 + r, 0), h - 1);
+    store(r, c, reinterpret_cast<const uchar4*>(rgba)[(size_t)sy * w + sx]);
+  }
+}
+
+// horizontal pass: patch row r, source column jj -> S values per channel;
+// tap(r, c, ch) is the staged value of channel ch, put(ch, r, x, v) stores
+template <int S, typename T, int NCH, typename Tap, typename Put>
+__device__ __forceinline__ void hpass(Tap tap, Put put) {
+  const int jj = threadIdx.x % T::JX;
+  for (int r = threadIdx.x / T::JX; r < T::PR; r += kThreads / T::JX) {
+#pragma unroll
+    for (int k = 0; k < S; k++) {
+      const float* wk = c_up.w[S][k];
+      const int c = jj + tap_base(S, k) + 1;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ch++)
+        put(ch, r, jj * S + k,
+            wk[0] * tap(r, c, ch) + wk[1] * tap(r, c + 1, ch) + wk[2] * tap(r, c + 2, ch) +
+                wk[3] * tap(r, c + 3, ch));
+    }
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void upscale_luma_kernel(const uint8_t* __restrict__ rgba,
+                                                                float* __restrict__ out, int w,
+                                                                int h, int P, int tiles_x) {
+  using T = Tile<S, false>;
+  constexpr int TX = T::TX, TY = T::TY;
+  __shared__ float s_src[T::PR][T::PCP];
+  __shared__ float s_h[T::PR][TX + 1];
+  const int tid = threadIdx.x;
+  const int tiles_y = gridDim.x / tiles_x;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int j0 = tx * T::JX, i0 = ty * T::JY;
+
+  stage_patch<T>(rgba, w, h, j0, i0, [&](int r, int c, uchar4 p) {
+    s_src[r][c] = luma_of((float)p.x, (float)p.y, (float)p.z);
+  });
+  __syncthreads();
+  hpass<S, T, 1>([&](int r, int c, int) { return s_src[r][c]; },
+                 [&](int, int r, int x, float v) { s_h[r][x] = v; });
+  __syncthreads();
+
+  // the plane rows and columns this tile owns: its own pixels shifted by the
+  // margin m, plus the margin itself on the image's edges
+  const int W = w * S, H = h * S, m = P / 2;
+  const int X0 = tx * TX, Y0 = ty * TY;
+  const int Xp0 = tx == 0 ? 0 : m + X0, Xp1 = tx == tiles_x - 1 ? W + P : m + X0 + TX;
+  const int Yp0 = ty == 0 ? 0 : m + Y0, Yp1 = ty == tiles_y - 1 ? H + P : m + Y0 + TY;
+  const int n = Xp1 - Xp0;
+  const size_t pitch = (size_t)W + P;
+
+  // LPR lanes share a row; each stores 16 bytes where the row's address allows
+  constexpr int LPR = TX <= 64 ? 16 : 32, RPI = kThreads / LPR;
+  const int l = tid % LPR;
+  for (int Y = Yp0 + tid / LPR; Y < Yp1; Y += RPI) {
+    const int Yi = min(max(Y - m, 0), H - 1);
+    const int jy = Yi / S, ky = Yi - jy * S;
+    const int rb = jy - i0 + tap_base(S, ky) + 1;  // patch row of the first tap
+    float wv[4];
+    phase_weights<S>(ky, wv);
+    const float w0 = wv[0], w1 = wv[1], w2 = wv[2], w3 = wv[3];
+    auto val = [&](int X) {
+      const int cx = min(max(X - m, 0), W - 1) - X0;
+      return w0 * s_h[rb][cx] + w1 * s_h[rb + 1][cx] + w2 * s_h[rb + 2][cx] + w3 * s_h[rb + 3][cx];
+    };
+    float* orow = out + (size_t)Y * pitch;
+    // floats up to the first 16-byte boundary, float4 groups, the rest
+    const int head = min((int)(((16 - ((uintptr_t)(orow + Xp0) & 15)) & 15) >> 2), n);
+    if (l < head) orow[Xp0 + l] = val(Xp0 + l);
+    const int ng = (n - head) >> 2;
+    for (int g = l; g < ng; g += LPR) {
+      const int X = Xp0 + head + 4 * g;
+      *reinterpret_cast<float4*>(orow + X) = make_float4(val(X), val(X + 1), val(X + 2), val(X + 3));
+    }
+    const int X = Xp0 + head + 4 * ng + l;
+    if (X < Xp1) orow[X] = val(X);
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void upscale_compose_kernel(
+    const uint8_t* __restrict__ rgba, const float* __restrict__ nl, uint8_t* __restrict__ rgb,
+    int w, int h, int tiles_x) {
+  using T = Tile<S, true>;
+  constexpr int TX = T::TX, TY = T::TY;
+  constexpr int RB = kThreads / 32;    // output rows per batch
+  constexpr int STG = 16 + 3 * TX;     // staged row: up to 15 bytes of skew + the pixels
+  __shared__ uchar4 s_src[T::PR][T::PCP];
+  __shared__ float s_h[3][T::PR][TX + 1];
+  __shared__ __attribute__((aligned(16))) uint8_t s_out[RB][STG];
+  const int tid = threadIdx.x;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int j0 = tx * T::JX, i0 = ty * T::JY;
+
+  stage_patch<T>(rgba, w, h, j0, i0, [&](int r, int c, uchar4 p) { s_src[r][c] = p; });
+  __syncthreads();
+  hpass<S, T, 3>(
+      [&](int r, int c, int ch) {
+        const uchar4 p = s_src[r][c];
+        return (float)(ch == 0 ? p.x : ch == 1 ? p.y : p.z);
+      },
+      [&](int ch, int r, int x, float v) { s_h[ch][r][x] = v; });
+  __syncthreads();
+
+  const int W = w * S, H = h * S;
+  const int X0 = tx * TX, Y0 = ty * TY;
+  const int ncol = min(TX, W - X0), nrow = min(TY, H - Y0);
+  const int nb = 3 * ncol;  // bytes of one output row of the tile
+  const int c5 = tid & 31, rr = tid >> 5;
+  for (int yb = 0; yb < nrow; yb += RB) {
+    const bool live = yb + rr < nrow;
+    const int Y = Y0 + yb + rr;
+    uint8_t* grow = rgb + ((size_t)Y * W + X0) * 3;
+    // the row is staged in LDS at the skew its global address has, so that
+    // 16-byte chunks of the two line up
+    const int o = (int)((uintptr_t)grow & 15);
+    if (live) {
+      const int jy = Y / S, ky = Y - jy * S;
+      const int rb = jy - i0 + tap_base(S, ky) + 1;
+      float wv[4];
+      phase_weights<S>(ky, wv);
+      const float w0 = wv[0], w1 = wv[1], w2 = wv[2], w3 = wv[3];
+      const float* lrow = nl + (size_t)Y * W + X0;
+#pragma unroll
+      for (int i = 0; i < TX / 32; i++) {
+        const int cx = c5 + 32 * i;
+        if (cx < ncol) {
+          auto val = [&](int ch) {
+            return w0 * s_h[ch][rb][cx] + w1 * s_h[ch][rb + 1][cx] + w2 * s_h[ch][rb + 2][cx] +
+                   w3 * s_h[ch][rb + 3][cx];
+          };
+          compose_px(val(0), val(1), val(2), lrow[cx], &s_out[rr][o + 3 * cx]);
+        }
+      }
+    }
+    __syncthreads();
+    if (live) {
+      // bytes up to the first 16-byte boundary, 16-byte chunks, the rest
+      const int head = min((16 - o) & 15, nb);
+      if (c5 < head) grow[c5] = s_out[rr][o + c5];
+      const int nch = (nb - head) >> 4;  // <= 3*TX/16 <= 24 of the row's 32 lanes
+      if (c5 < nch)
+        *reinterpret_cast<uint4*>(grow + head + 16 * c5) =
+            *reinterpret_cast<const uint4*>(&s_out[rr][o + head + 16 * c5]);
+      const int t = head + 16 * nch + c5;
+      if (t < nb) grow[t] = s_out[rr][o + t];
+    }
+    __syncthreads();
+  }
+}
+
+inline uint32_t tiles(uint32_t n, int t) { return (n + t - 1) / t; }
+
+}  // namespace
+
+int upscale_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint32_t scale,
+                 uint32_t pad, hipStream_t s) {
+  SRCNN_PROFILE("upscale_luma", s);
+#define SRCNN_UP_LUMA(S)                                                                        \
+  {                                                                                             \
+    const uint32_t tx = tiles(w, Tile<S, false>::JX), ty = tiles(h, Tile<S, false>::JY); \
+    hipLaunchKernelGGL(upscale_luma_kernel<S>, dim3(tx* ty), dim3(kThreads), 0, s, rgba, plane, \
+                       (int)w, (int)h, (int)pad, (int)tx);                                      \
+  }
+  switch (scale) {
+    case 1: SRCNN_UP_LUMA(1); break;
+    case 2: SRCNN_UP_LUMA(2); break;
+    case 3: SRCNN_UP_LUMA(3); break;
+    case 4: SRCNN_UP_LUMA(4); break;
+    default: return fail(SRCNN_ERR_INVALID, "upscale_luma: scale %u has no kernel", scale);
+  }
+#undef SRCNN_UP_LUMA
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+
+int upscale_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
+                    uint32_t scale, hipStream_t s) {
+  SRCNN_PROFILE("upscale_compose", s);
+#define SRCNN_UP_COMPOSE(S)                                                                     \
+  {                                                                                             \
+    const uint32_t tx = tiles(w, Tile<S, true>::JX), ty = tiles(h, Tile<S, true>::JY);   \
+    hipLaunchKernelGGL(upscale_compose_kernel<S>, dim3(tx* ty), dim3(kThreads), 0, s, rgba, nl, \
+                       rgb, (int)w, (int)h, (int)tx);                                           \
+  }
+  switch (scale) {
+    case 1: SRCNN_UP_COMPOSE(1); break;
+    case 2: SRCNN_UP_COMPOSE(2); break;
+    case 3: SRCNN_UP_COMPOSE(3); break;
+    case 4: SRCNN_UP_COMPOSE(4); break;
+    default: return fail(SRCNN_ERR_INVALID, "upscale_compose: scale %u has no kernel", scale);
+  }
+#undef SRCNN_UP_COMPOSE
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+
+int preload_upscale() {
+  const void* k[] = {(const void*)upscale_luma_kernel<1>,    (const void*)upscale_luma_kernel<2>,
+                     (const void*)upscale_luma_kernel<3>,    (const void*)upscale_luma_kernel<4>,
+                     (const void*)upscale_compose_kernel<1>, (const void*)upscale_compose_kernel<2>,
+                     (const void*)upscale_compose_kernel<3>, (const void*)upscale_compose_kernel<4>};
+  return resolve_kernels(k, 8);
+}
+
+}  // namespace srcnn

@@ -222,6 +222,39 @@ Event ConfigBasedDataPipeline::forward(LayerAllocationPool& l1, LayerAllocationP
                        _out_3_gpu_buf, &e2);
 }
 
+void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, ImageData& result) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  require(scale >= 1 && scale <= 4, "super_resolve: scale must be 1, 2, 3 or 4");
+  require(low_res.w > 0 && low_res.h > 0, "super_resolve: empty image");
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  const size_t W = size_t(low_res.w) * scale, H = size_t(low_res.h) * scale;
+  const size_t ws = srcnn_upscale_workspace_bytes(&nt, low_res.w, low_res.h, scale);
+  require(ws > 0, std::string("super_resolve: ") + srcnn_last_error());
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, low_res.w, low_res.h);
+  _context->write_image(rgba, low_res, true);
+  MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, W * H * 3);
+  void* wsp = scratch(ws);
+  if (!_upscale_kernel) {
+    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
+                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
+                             " -D F3=" + std::to_string(nt.f3);
+    _upscale_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale", 0, 0, 0, false, args);
+  }
+  {
+    srcnn::Context::Launch l(*_context, *_upscale_kernel);
+    check(srcnn_upscale(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), low_res.w, low_res.h, scale,
+                        _context->fptr(_flat_params), static_cast<uint8_t*>(_context->ptr(rgb)), wsp, ws,
+                        _context->stream()),
+          "upscale");
+  }
+  result = ImageData(int(W), int(H), 3);
+  _context->read_buffer(rgb, 0, result.data.size(), result.data.data(), true);
+  _context->raw_memory(rgb)->release();
+  _context->raw_memory(rgba)->release();
+}
+
 // ---------------------------------------------------------------- training
 
 Event ConfigBasedDataPipeline::backpropagate(LayerAllocationPool& l1, LayerAllocationPool& l2,

@@ -105,6 +105,13 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * reference's loader skips), and a parameters file that holds them resumes
    * the pipeline-owned momentum buffers from them */
   void set_save_momentum(bool on) { _save_momentum = on; }
+  /** Low-resolution image in, image of `scale` (1..4) times the size out,
+   * all on the device: uploads the RGBA, makes one srcnn_upscale call on the
+   * pipeline's flat parameters (bicubic luma into the edge-replicated padded
+   * plane, mean subtraction, the net, composition with the bicubic colours)
+   * and reads the RGB result back.  Every output pixel passes through the
+   * net: no border frame is left, also with scale 1. */
+  void super_resolve(ImageData& low_res, unsigned scale, ImageData& result);
   /** L3 output of the last forward / execute_batch chunk */
   MemoryHandle result_buffer() const { return _out_3_gpu_buf; }
   /** the flat [gW1|gB1|gW2|gB2|gW3|gB3] buffer (gpu_nullptr before training
@@ -170,6 +177,7 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _layer_2_deltas_kernel = nullptr;
   Kernel* _train_kernel = nullptr;
   Kernel* _forward_kernel = nullptr;
+  Kernel* _upscale_kernel = nullptr;
   Kernel* _update_all_kernel = nullptr;
   Kernel* _allreduce_kernel = nullptr;
   MemoryHandle _comm_scalar = gpu_nullptr;

@@ -157,6 +157,48 @@ Event DataPipeline::swap_luma(ImageData& img, MemoryHandle& org_img, MemoryHandl
   return _context->mark();
 }
 
+Event DataPipeline::upscale_luma(ImageData& img, MemoryHandle& raw_img, MemoryHandle& luma_padded,
+                                 size_t scale, size_t padding, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(scale >= 1 && scale <= 4, "upscale_luma: scale must be 1, 2, 3 or 4");
+  _context->wait(ev);
+  size_t px = size_t(img.w) * img.h;
+  size_t plane = (img.w * scale + padding) * (img.h * scale + padding) * sizeof(float);
+  if (!SRCNN_HAS_SIZE(raw_img, px * 4)) raw_img = _context->create_image(srcnn::MEM_READ_WRITE, img.w, img.h);
+  _context->write_image(raw_img, img, true);
+  if (!SRCNN_HAS_SIZE(luma_padded, plane)) luma_padded = _context->allocate(srcnn::MEM_READ_WRITE, plane);
+  // (made at first use, so that the profile listing of a run that does not
+  // upscale stays the reference's)
+  if (!_upscale_luma_kernel)
+    _upscale_luma_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "upscale_luma");
+  srcnn::Context::Launch l(*_context, *_upscale_luma_kernel);
+  check(srcnn_upscale_luma(static_cast<const uint8_t*>(_context->ptr(raw_img)), _context->fptr(luma_padded),
+                           img.w, img.h, uint32_t(scale), uint32_t(padding), _context->stream()),
+        "upscale_luma");
+  return _context->mark();
+}
+
+Event DataPipeline::upscale_compose(ImageData& img, MemoryHandle org_img, MemoryHandle new_luma,
+                                    MemoryHandle& target, size_t scale, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(scale >= 1 && scale <= 4, "upscale_compose: scale must be 1, 2, 3 or 4");
+  _context->wait(ev);
+  size_t out_px = size_t(img.w) * scale * img.h * scale;
+  if (!SRCNN_HAS_SIZE(org_img, size_t(img.w) * img.h * 4))
+    throw std::runtime_error("Invalid size of the original image buffer");
+  if (!SRCNN_HAS_SIZE(new_luma, out_px * sizeof(float)))
+    throw std::runtime_error("Invalid size of new luma buffer");
+  if (!SRCNN_HAS_SIZE(target, out_px * 3)) target = _context->allocate(srcnn::MEM_READ_WRITE, out_px * 3);
+  if (!_upscale_compose_kernel)
+    _upscale_compose_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "upscale_compose");
+  srcnn::Context::Launch l(*_context, *_upscale_compose_kernel);
+  check(srcnn_upscale_compose(static_cast<const uint8_t*>(_context->ptr(org_img)), _context->fptr(new_luma),
+                              static_cast<uint8_t*>(_context->ptr(target)), img.w, img.h, uint32_t(scale),
+                              _context->stream()),
+        "upscale_compose");
+  return _context->mark();
+}
+
 float DataPipeline::sum(MemoryHandle data, bool squared, Event* ev) {
   check_initialized(LOAD_KERNEL_MISC);
   _context->wait(ev);

@@ -56,6 +56,20 @@ class DataPipeline {
                   MemoryHandle& target, size_t new_luma_w, size_t new_luma_h,
                   Event* ev = nullptr);
 
+  /** Extension (the reference expects an already scaled input): upload the
+   * low-resolution `img` to raw_img and write its bicubic x `scale` luma,
+   * edge-replicated by the margin of `total_padding`, to luma_padded:
+   * (scale*h + total_padding) x (scale*w + total_padding) floats
+   * (srcnn_upscale_luma). */
+  Event upscale_luma(ImageData&, MemoryHandle& gpu_buf_raw_img, MemoryHandle& gpu_buf_luma_padded,
+                     size_t scale, size_t total_padding, Event* ev = nullptr);
+
+  /** Extension: RGB image of scale*w x scale*h made of the new luma (that
+   * size) and the bicubic x `scale` colours of `img`, which the caller has
+   * uploaded to gpu_buf_org_img (srcnn_upscale_compose). */
+  Event upscale_compose(ImageData&, MemoryHandle gpu_buf_org_img, MemoryHandle gpu_buf_new_luma,
+                        MemoryHandle& target, size_t scale, Event* ev = nullptr);
+
   /** Forward of one layer over `sample_count` samples (reference :358-410). */
   Event execute_layer(Kernel&, const LayerData&, LayerAllocationPool&, MemoryHandle& gpu_buf_in,
                       size_t input_w, size_t input_h, size_t sample_count,
@@ -125,6 +139,8 @@ class DataPipeline {
   Kernel* _luma_kernel_norm = nullptr;
   Kernel* _luma_kernel_raw = nullptr;
   Kernel* _swap_luma_kernel = nullptr;
+  Kernel* _upscale_luma_kernel = nullptr;
+  Kernel* _upscale_compose_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;
   Kernel* _sum_squared_kernel = nullptr;

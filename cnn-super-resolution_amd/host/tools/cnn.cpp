@@ -1,11 +1,18 @@
 // cnn -- the command line of the reference (src/Main_cl.cpp) on the MI355X
 // pipeline:
 //
-//   cnn [-h] [train] [dry] [profile] -c CONFIG -i IN [-o OUT] [-e EPOCHS]
-//       [--seed N] [--device D] [--devices N] [--validation-percent P]
-//       [--mini-batches M] [--save-momentum]
+//   cnn [-h] [train | upscale] [dry] [profile] -c CONFIG -i IN [-o OUT]
+//       [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]
+//       [--validation-percent P] [--mini-batches M] [--save-momentum]
 //
-// forward:  IN is an image (JPEG / PNG / PNM), OUT the upscaled result image
+// forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
+//           result image of the same size (its outermost total_padding / 2
+//           pixels are the input's)
+// upscale:  (extension) IN is a low-resolution image, OUT the image of S times
+//           the size (--scale 1, 2, 3 or 4; default 2): bicubic resampling, the
+//           net and the composition all run on the device (srcnn_upscale), and
+//           every output pixel passes through the net.  --scale 1 is the
+//           "same size, no border frame" mode for inputs that are already scaled.
 // train:    IN is a directory of <name>_large.<ext> / <name>_small.<ext> pairs
 //           (ground truth / degraded input, tools/make_samples.py makes
 //           them), OUT the parameters.json written at the end.
@@ -50,7 +57,9 @@ using namespace cnn_sr;
 namespace {
 
 struct Args {
-  bool train = false, dry = false, profile = false, help = false, version = false;
+  bool train = false, upscale = false, dry = false, profile = false, help = false, version = false;
+  unsigned scale = 2;      // upscale: --scale
+  bool scale_set = false;
   std::string config, in, out;
   size_t epochs = 0;
   uint64_t seed = 0;
@@ -67,18 +76,24 @@ struct Args {
 
 void usage() {
   std::cout
-      << "usage: cnn [-h] [train] [dry] [profile] -c CONFIG -i IN [-o OUT] [-e EPOCHS]\n"
-         "           [--seed N] [--device D] [--devices N] [--validation-percent P]\n"
-         "           [--mini-batches M] [--save-momentum]\n\n"
+      << "usage: cnn [-h] [train | upscale] [dry] [profile] -c CONFIG -i IN [-o OUT]\n"
+         "           [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]\n"
+         "           [--validation-percent P] [--mini-batches M] [--save-momentum]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
+         "  upscale               upscale mode: IN is a low-resolution image, OUT the image\n"
+         "                        of --scale times the size (bicubic + net on the device;\n"
+         "                        no un-enhanced border frame)\n"
          "  dry                   do not store the result\n"
          "  profile               print kernel execution times\n"
          "  -c, --config CONFIG   CNN configuration (config.json)\n"
-         "  -i, --in IN           image during forward, samples directory during training\n"
+         "  -i, --in IN           image during forward / upscale, samples directory during\n"
+         "                        training\n"
          "  -o, --out OUT         output path (result image or new parameters file)\n"
          "  -e, --epochs EPOCHS   number of epochs during training\n"
+         "  --scale S             upscale factor 1, 2, 3 or 4 (default 2; upscale mode only;\n"
+         "                        1: same size, every pixel through the net)\n"
          "  --seed N              seed of the random parameters and the epoch shuffles\n"
          "  --device D            HIP device index (default 0)\n"
          "  --devices N           train data-parallel on devices D .. D+N-1 (default 1)\n"
@@ -101,6 +116,14 @@ bool parse(int argc, char** argv, Args& a) {
     if (s == "-h" || s == "--help" || s == "help") a.help = true;
     else if (s == "--version") a.version = true;
     else if (s == "train") a.train = true;
+    else if (s == "upscale") a.upscale = true;
+    else if (s == "--scale") {
+      const std::string v = value("--scale");
+      if (v != "1" && v != "2" && v != "3" && v != "4")
+        throw std::runtime_error("--scale must be 1, 2, 3 or 4");
+      a.scale = unsigned(v[0] - '0');
+      a.scale_set = true;
+    }
     else if (s == "dry") a.dry = true;
     else if (s == "profile") a.profile = true;
     else if (s == "-c" || s == "--config") a.config = value("--config");
@@ -122,6 +145,8 @@ bool parse(int argc, char** argv, Args& a) {
     else throw std::runtime_error("unknown argument '" + s + "'");
   }
   if (a.help || a.version) return false;
+  if (a.scale_set && !a.upscale) throw std::runtime_error("--scale needs the upscale mode");
+  if (a.upscale && a.train) throw std::runtime_error("train and upscale are different modes");
   if (a.config.empty() || a.in.empty()) throw std::runtime_error("--config and --in are required");
   if (a.devices < 1) throw std::runtime_error("--devices must be >= 1");
   if (a.same_device && !a.host_exchange)
@@ -179,6 +204,19 @@ int forward(ConfigBasedDataPipeline& p, const Args& a) {
   p.forward(pools.layer_1, pools.layer_2, pools.layer_3, sample);
   if (!a.dry && !a.out.empty()) p.write_result_image(a.out.c_str(), img, sample);
   ctx.block();
+  return 0;
+}
+
+/** `cnn upscale`: the low-resolution image through srcnn_upscale */
+int upscale(ConfigBasedDataPipeline& p, const Args& a) {
+  ImageData img, res;
+  srcnn::image::load(a.in, img, 4);
+  p.super_resolve(img, a.scale, res);
+  if (!a.dry && !a.out.empty()) {
+    std::cout << "Saving result image to: '" << a.out << "'" << std::endl;
+    srcnn::image::write(a.out.c_str(), res);
+  }
+  p.context()->block();
   return 0;
 }
 
@@ -446,6 +484,10 @@ int main(int argc, char** argv) {
     std::cout << "Training mode, epochs: " << a.epochs << std::endl
               << "Training samples directory: " << a.in << std::endl
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
+  else if (a.upscale)
+    std::cout << "Upscale mode, scale: " << a.scale << std::endl
+              << "Input image: " << a.in << std::endl
+              << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   else
     std::cout << "Forward mode" << std::endl
               << "Input image: " << a.in << std::endl
@@ -462,7 +504,9 @@ int main(int argc, char** argv) {
       ConfigBasedDataPipeline pipeline(cfg, &context);
       if (a.seeded) pipeline.set_random_seed(a.seed);
       pipeline.init(DataPipeline::LOAD_KERNEL_ALL);
-      rc = a.train ? train(pipeline, a, a.seeded ? a.seed : std::random_device{}()) : forward(pipeline, a);
+      rc = a.train     ? train(pipeline, a, a.seeded ? a.seed : std::random_device{}())
+           : a.upscale ? upscale(pipeline, a)
+                       : forward(pipeline, a);
     }
     return rc;
   } catch (const std::exception& e) {

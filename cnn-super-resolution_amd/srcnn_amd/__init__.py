@@ -82,6 +82,10 @@ SIGNATURES = {
     "srcnn_sub_mean": (_I, [_P, _S, _P, _P, _S, _P]),
     "srcnn_extract_luma": (_I, [_P, _P, _U, _U, _I, _P]),
     "srcnn_swap_luma": (_I, [_P, _P, _P, _U, _U, _U, _U, _P]),
+    "srcnn_upscale_luma": (_I, [_P, _P, _U, _U, _U, _U, _P]),
+    "srcnn_upscale_compose": (_I, [_P, _P, _P, _U, _U, _U, _P]),
+    "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
+    "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
     "srcnn_net_param_count": (_S, [_NP]),
     "srcnn_train_workspace_bytes": (_S, [_NP, _U, _U, _U]),
@@ -305,6 +309,18 @@ def swap_luma(rgba, new_luma, rgb, w, h, luma_w, luma_h, s=None):
     _call("srcnn_swap_luma", ptr(rgba), ptr(new_luma), ptr(rgb), w, h, luma_w, luma_h, s)
 
 
+def upscale_luma(rgba, luma_padded, w, h, scale, pad, s=None):
+    """rgba [h][w][4] u8 -> bicubic x scale luma, edge-replicated into the
+    padded plane [(scale*h+pad)][(scale*w+pad)] f32 (srcnn_upscale_luma)."""
+    _call("srcnn_upscale_luma", ptr(rgba), ptr(luma_padded), w, h, scale, pad, s)
+
+
+def upscale_compose(rgba, new_luma, rgb, w, h, scale, s=None):
+    """bicubic x scale of the source's r, g, b + new_luma [scale*h][scale*w]
+    -> rgb [scale*h][scale*w][3] u8 (srcnn_upscale_compose)."""
+    _call("srcnn_upscale_compose", ptr(rgba), ptr(new_luma), ptr(rgb), w, h, scale, s)
+
+
 # ---- network level ----
 def net_offsets(net):
     arr = (_S * 6)()
@@ -396,6 +412,18 @@ def forward_workspace_bytes(net, w, h, batch):
 def forward(net, X, w, h, batch, params, out, ws, ws_bytes, s=None):
     _call("srcnn_forward", ctypes.byref(net), ptr(X), w, h, batch, ptr(params), ptr(out), ptr(ws),
           ws_bytes, s)
+
+
+def upscale_workspace_bytes(net, w, h, scale):
+    return _lib.srcnn_upscale_workspace_bytes(ctypes.byref(net), w, h, scale)
+
+
+def upscale(net, rgba, w, h, scale, params, rgb, ws, ws_bytes, s=None):
+    """Low-resolution rgba [h][w][4] u8 -> super-resolved rgb
+    [scale*h][scale*w][3] u8 (srcnn_upscale): upscale_luma, sub_mean over the
+    padded plane, forward, upscale_compose."""
+    _call("srcnn_upscale", ctypes.byref(net), ptr(rgba), w, h, scale, ptr(params), ptr(rgb),
+          ptr(ws), ws_bytes, s)
 
 
 def set_path(p):

@@ -176,13 +176,42 @@ SRCNN_API int srcnn_swap_luma(const uint8_t* rgba, const float* new_luma,
                               uint32_t luma_w, uint32_t luma_h,
                               srcnn_stream_t stream);
 
+/* Upscaling front and back end (an MI355X extension; the reference expects an
+ * input that is already scaled and has no counterpart).  scale s is 1, 2, 3
+ * or 4; W = s*w, H = s*h.  The resampling is the separable Keys bicubic
+ * (a = -0.5) at half-pixel centres with source indices clamped to the image,
+ * fp32, horizontal pass first (DESIGN.md 10.1 is the spec).
+ *
+ * srcnn_upscale_luma: rgba [h][w][4] u8 -> luma_padded [(H+pad)][(W+pad)] f32:
+ * plane[Y][X] is the bicubic value of the normalised luma (srcnn_extract_luma
+ * with normalize) at X' = clamp(X - pad/2, 0, W-1), Y' = clamp(Y - pad/2, 0,
+ * H-1), i.e. the upscaled luma with its edge replicated into a margin of
+ * pad/2 pixels on the left and top and pad - pad/2 on the right and bottom.
+ * A net with total padding `pad` turns this plane into exactly W x H outputs.
+ * With s = 1 the interior is srcnn_extract_luma's output bit for bit.
+ *
+ * srcnn_upscale_compose: the same bicubic applied to the source's r, g, b
+ * (unclamped floats) + new_luma [H][W] -> rgb [H][W][3] u8, with
+ * srcnn_swap_luma's constants, clamp and truncation.  With s = 1 it is
+ * srcnn_swap_luma(w, h, w, h) byte for byte.
+ *
+ * SRCNN_ERR_INVALID: scale outside 1..4, w or h zero, a null buffer, or a size
+ * beyond the kernels' 32-bit index (the plane's floats and the rgb bytes must
+ * each number at most 2^31-1). */
+SRCNN_API int srcnn_upscale_luma(const uint8_t* rgba, float* luma_padded, uint32_t w, uint32_t h,
+                                 uint32_t scale, uint32_t pad, srcnn_stream_t stream);
+SRCNN_API int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* rgb,
+                                    uint32_t w, uint32_t h, uint32_t scale,
+                                    srcnn_stream_t stream);
+
 /* ---- network level: ConfigBasedDataPipeline (src/ConfigBasedDataPipeline.cpp) ---- */
 typedef struct srcnn_net {
   uint32_t n1, n2, f1, f2, f3; /* Config n1,n2,f1,f2,f3 (src/Config.hpp:27-28) */
 } srcnn_net;
 
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
- * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward) launch for this net.
+ * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale) launch
+ * for this net.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -209,7 +238,8 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *   - the call writes nothing outside [ws, ws + ws_bytes) and the documented
  *     extent of its outputs (grads: srcnn_net_param_count floats; sq_err: one
  *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
- *     A3 extent; srcnn_train_activations: the three extents it documents);
+ *     A3 extent; srcnn_train_activations: the three extents it documents;
+ *     rgb: 3*W*H bytes);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
@@ -245,6 +275,25 @@ SRCNN_API int srcnn_forward(const srcnn_net* net, const float* X, uint32_t w,
                             uint32_t h, uint32_t batch, const float* params,
                             float* out, void* ws, size_t ws_bytes,
                             srcnn_stream_t stream);
+
+/* Low-resolution image in, super-resolved image out, on the device:
+ * srcnn_upscale_luma (pad = f1+f2+f3-3) -> srcnn_sub_mean over the whole
+ * padded plane (what the net sees; as in the reference flow the mean is not
+ * added back) -> srcnn_forward -> srcnn_upscale_compose.  rgba [h][w][4] u8 ->
+ * rgb [scale*h][scale*w][3] u8; every output pixel passes through the net, no
+ * border frame is left.  Works for every net srcnn_forward accepts and is
+ * byte-identical to those four calls; stream-ordered, no host synchronisation,
+ * no allocation.  `ws` holds the plane, the net output, the reduction scratch
+ * and the forward workspace (each 256-byte aligned) under the memory contract
+ * at srcnn_train_workspace_bytes.  srcnn_upscale_workspace_bytes returns 0 for
+ * an invalid net, scale or size.  Errors as srcnn_upscale_luma, plus
+ * SRCNN_ERR_INVALID for an invalid net and SRCNN_ERR_WORKSPACE for a
+ * workspace that is too small. */
+SRCNN_API size_t srcnn_upscale_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                               uint32_t scale);
+SRCNN_API int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h,
+                            uint32_t scale, const float* params, uint8_t* rgb, void* ws,
+                            size_t ws_bytes, srcnn_stream_t stream);
 
 /* ---- profiling: the reference's `profile` mode (src/opencl/Kernel.cpp:108-116,
  * src/opencl/Context.cpp:88-96) without blocking per launch: when enabled,
