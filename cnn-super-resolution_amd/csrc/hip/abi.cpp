@@ -94,6 +94,57 @@ int up_dims(const char* who, uint32_t w, uint32_t h, uint32_t scale, uint32_t pa
   return SRCNN_OK;
 }
 
+// srcnn_downscale_rgba / srcnn_make_pairs: the source against the scale and
+// against what downscale_rgba_kernel can index (pixel offsets below 2^31)
+int down_dims(const char* who, uint32_t W, uint32_t H, uint32_t scale) {
+  SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
+  SRCNN_REQUIRE(W >= scale && H >= scale, "%s: image %ux%u is smaller than the scale %u", who, W, H,
+                scale);
+  SRCNN_REQUIRE((uint64_t)W * H <= 0x7fffffffull,
+                "%s: %ux%u exceeds the kernel's 32-bit index: the source's pixels must number at "
+                "most 2^31-1",
+                who, W, H);
+  return SRCNN_OK;
+}
+
+// srcnn_gather_tiles: the grid against the plane and against what
+// gather_tiles_kernel can index (int coordinates, one workgroup per tile)
+int gather_dims(const char* who, uint32_t pw, uint32_t ph, uint32_t x0, uint32_t y0,
+                uint32_t stride, uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th) {
+  SRCNN_REQUIRE(stride > 0 && nx > 0 && ny > 0 && tw > 0 && th > 0,
+                "%s: stride(%u), grid %ux%u and tile %ux%u must be > 0", who, stride, nx, ny, tw, th);
+  SRCNN_REQUIRE((uint64_t)x0 + (uint64_t)(nx - 1) * stride + tw <= pw &&
+                    (uint64_t)y0 + (uint64_t)(ny - 1) * stride + th <= ph,
+                "%s: %ux%u tiles of %ux%u from (%u, %u) at stride %u leave the %ux%u plane", who, nx,
+                ny, tw, th, x0, y0, stride, pw, ph);
+  SRCNN_REQUIRE((uint64_t)pw * ph <= 0x7fffffffull && (uint64_t)nx * ny <= 0x7fffffffull,
+                "%s: plane %ux%u or grid %ux%u exceeds the kernel's 32-bit index: the plane's floats "
+                "and the tiles must each number at most 2^31-1",
+                who, pw, ph, nx, ny);
+  return SRCNN_OK;
+}
+
+// regions of the make_pairs workspace: low-resolution image | X plane
+// [Hc][Wc] | T plane [H][W], each 256-byte aligned
+struct PairWs {
+  uint32_t w, h, Wc, Hc;
+  size_t small, xplane, tplane, total;  // byte offsets of the regions, and their sum
+};
+int pair_ws(const char* who, uint32_t W, uint32_t H, uint32_t scale, PairWs* L) {
+  if (int rc = down_dims(who, W, H, scale)) return rc;
+  L->w = W / scale;
+  L->h = H / scale;
+  UpDims u;
+  if (int rc = up_dims(who, L->w, L->h, scale, 0, &u)) return rc;
+  L->Wc = u.W;
+  L->Hc = u.H;
+  L->small = 0;
+  L->xplane = L->small + align_up((size_t)L->w * L->h * 4);
+  L->tplane = L->xplane + align_up((size_t)L->Wc * L->Hc * sizeof(float));
+  L->total = L->tplane + align_up((size_t)W * H * sizeof(float));
+  return SRCNN_OK;
+}
+
 size_t grad_ws_bytes(uint32_t n_prev, uint32_t n_cur, uint32_t f, uint32_t ow, uint32_t oh,
                      uint32_t batch) {
   size_t b = 0;
@@ -270,6 +321,72 @@ int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* r
   return srcnn::upscale_compose(rgba, new_luma, rgb, w, h, scale, as_stream(stream));
 }
 
+int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
+                         uint32_t scale, srcnn_stream_t stream) {
+  if (int rc = down_dims("downscale_rgba", W, H, scale)) return rc;
+  SRCNN_REQUIRE(rgba && small, "downscale_rgba: null buffer");
+  return srcnn::downscale_rgba(rgba, small, W, H, scale, as_stream(stream));
+}
+
+int srcnn_gather_tiles(const float* plane, uint32_t pw, uint32_t ph, uint32_t x0, uint32_t y0,
+                       uint32_t stride, uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th,
+                       int sub_mean, float* tiles, float* means, srcnn_stream_t stream) {
+  if (int rc = gather_dims("gather_tiles", pw, ph, x0, y0, stride, nx, ny, tw, th)) return rc;
+  SRCNN_REQUIRE(plane && tiles, "gather_tiles: null buffer");
+  return srcnn::gather_tiles(plane, pw, x0, y0, stride, nx, ny, tw, th, sub_mean, tiles, means,
+                             as_stream(stream));
+}
+
+size_t srcnn_make_pairs_count(uint32_t W, uint32_t H, uint32_t scale, uint32_t tile,
+                              uint32_t stride, uint32_t* nx, uint32_t* ny) {
+  if (nx) *nx = 0;
+  if (ny) *ny = 0;
+  if (scale < 1 || scale > 4 || W < scale || H < scale || tile == 0 || stride == 0) return 0;
+  const uint32_t Wc = W / scale * scale, Hc = H / scale * scale;
+  if (tile > Wc || tile > Hc) return 0;
+  const uint32_t gx = (Wc - tile) / stride + 1, gy = (Hc - tile) / stride + 1;
+  if ((uint64_t)gx * gy > 0x7fffffffull) return 0;
+  if (nx) *nx = gx;
+  if (ny) *ny = gy;
+  return (size_t)gx * gy;
+}
+
+size_t srcnn_make_pairs_workspace_bytes(uint32_t W, uint32_t H, uint32_t scale) {
+  PairWs L;
+  return pair_ws("make_pairs", W, H, scale, &L) ? 0 : L.total;
+}
+
+int srcnn_make_pairs(const uint8_t* rgba, uint32_t W, uint32_t H, uint32_t scale, uint32_t tile,
+                     uint32_t stride, float* X, float* T, void* ws, size_t ws_bytes,
+                     srcnn_stream_t stream) {
+  PairWs L;
+  if (int rc = pair_ws("make_pairs", W, H, scale, &L)) return rc;
+  SRCNN_REQUIRE(tile > 0 && stride > 0, "make_pairs: tile(%u) and stride(%u) must be > 0", tile,
+                stride);
+  uint32_t nx, ny;
+  SRCNN_REQUIRE(srcnn_make_pairs_count(W, H, scale, tile, stride, &nx, &ny) > 0,
+                "make_pairs: image %ux%u at scale %u holds no %ux%u tile (or more than 2^31-1)", W,
+                H, scale, tile, tile);
+  // (the two gathers' own checks, before the first launch)
+  if (int rc = gather_dims("make_pairs", L.Wc, L.Hc, 0, 0, stride, nx, ny, tile, tile)) return rc;
+  if (int rc = gather_dims("make_pairs", W, H, 0, 0, stride, nx, ny, tile, tile)) return rc;
+  SRCNN_REQUIRE(rgba && X && T && ws, "make_pairs: null buffer");
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "make_pairs: workspace %zu B < %zu B", ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  uint8_t* small = reinterpret_cast<uint8_t*>(p + L.small);
+  float* xplane = reinterpret_cast<float*>(p + L.xplane);
+  float* tplane = reinterpret_cast<float*>(p + L.tplane);
+  int rc;
+  if ((rc = srcnn_downscale_rgba(rgba, small, W, H, scale, stream))) return rc;
+  if ((rc = srcnn_upscale_luma(small, xplane, L.w, L.h, scale, 0, stream))) return rc;
+  if ((rc = srcnn_extract_luma(rgba, tplane, W, H, 1, stream))) return rc;
+  if ((rc = srcnn_gather_tiles(xplane, L.Wc, L.Hc, 0, 0, stride, nx, ny, tile, tile, 1, X, nullptr,
+                               stream)))
+    return rc;
+  return srcnn_gather_tiles(tplane, W, H, 0, 0, stride, nx, ny, tile, tile, 0, T, nullptr, stream);
+}
+
 // ---------------------------------------------------------------------------
 // network level
 // ---------------------------------------------------------------------------
@@ -295,7 +412,8 @@ int srcnn_preload(const srcnn_net* net) {
   if (int rc = srcnn_net_offsets(net, off)) return rc;
   int rc;
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
-      (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0)
+      (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0 ||
+      (rc = srcnn::preload_pairs()) < 0)
     return rc;
   return srcnn::preload_update();
 }

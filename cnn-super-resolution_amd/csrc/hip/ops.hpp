@@ -224,5 +224,15 @@ int upscale_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint
 int upscale_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
                     uint32_t scale, hipStream_t s);
 int preload_upscale();
+// pairs.hip: antialiased bicubic / scale (1..4) of rgba [H][W][4] into small
+// [H/scale][W/scale][4], and the cut of a grid of nx x ny tiles (tw x th,
+// origin (x0, y0), step `stride`) out of a float plane of pitch pw into
+// tiles [nx*ny][th][tw], each minus its own mean when sub_mean
+int downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H, uint32_t scale,
+                   hipStream_t s);
+int gather_tiles(const float* plane, uint32_t pw, uint32_t x0, uint32_t y0, uint32_t stride,
+                 uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th, int sub_mean, float* tiles,
+                 float* means, hipStream_t s);
+int preload_pairs();
 
 }  // namespace srcnn

@@ -1,0 +1,206 @@
+// pairs.hip -- training pairs from a full-size image on the device:
+//   downscale_rgba  rgba [H][W][4] u8 -> antialiased bicubic / S, [H/S][W/S][4] u8
+//                   (the inverse of upscale.hip's resampling: same Keys kernel,
+//                   stretched by S, half-pixel centres, replicated edges)
+//   gather_tiles    float plane [ph][pw] -> a grid of tiles [n][th][tw], each
+//                   optionally minus its own mean (the batch layout
+//                   srcnn_train_fwd_bwd reads)
+// The reference has no counterpart: its pairs are made on the host, one file
+// per sample.  The resampling is specified in DESIGN.md 11.1.
+//
+// downscale_rgba: one workgroup per tile of TX x TY output pixels (struct
+// Tile).  The source patch the tile's taps reach (S*(T-1) + NT per axis,
+// indices clamped to the image) is fetched once with one 4-byte load per
+// pixel and kept in LDS as the RGBA8 word; the horizontal pass writes the
+// patch's rows of TX values per channel to LDS; the vertical pass reads NT of
+// those rows per output into registers; one uchar4 store per output pixel.
+// The phase is the same for every output, so every weight index is a
+// compile-time value (uniform scalar loads from __constant__).
+#include "common.hpp"
+#include "keys.hpp"
+#include "ops.hpp"
+
+namespace srcnn {
+namespace {
+
+constexpr int kThreads = 256;
+
+// taps of scale s: source offsets o_min(s) .. s-1-o_min(s) from s*j, every
+// integer o with |o - (s-1)/2| / s < 2: 3 / 8 / 11 / 16 taps at s = 1 .. 4
+constexpr int o_min(int s) { return s % 2 ? -(3 * s + 1) / 2 + 1 : -3 * s / 2; }
+constexpr int n_taps(int s) { return s - 2 * o_min(s); }
+constexpr int kMaxTaps = n_taps(4);
+
+struct DownWeights {
+  float w[5][kMaxTaps];  // [scale][tap], computed in double, rounded once
+};
+constexpr DownWeights make_down_weights() {
+  DownWeights t{};
+  for (int s = 1; s <= 4; s++) {
+    double k[kMaxTaps] = {}, sum = 0;
+    for (int i = 0; i < n_taps(s); i++) {
+      k[i] = keys((o_min(s) + i - (s - 1) / 2.0) / s);
+      sum += k[i];
+    }
+    for (int i = 0; i < n_taps(s); i++) t.w[s][i] = (float)(k[i] / sum);
+  }
+  return t;
+}
+__constant__ DownWeights c_down = make_down_weights();
+
+// Tile geometry by LDS budget: 32 output pixels wide, so
+// that a tile's output rows are whole 128-byte lines and its patch rows 264 -
+// 560 contiguous bytes; 16 rows at S <= 2 (26 KB of LDS at S = 2: 6
+// workgroups per CU), 8 at S >= 3, where the patch grows with S^2 (26 / 42 KB
+// at S = 3 / 4: 6 / 3 workgroups per CU; 16 rows would be 71 KB at S = 4).
+template <int S>
+struct Tile {
+  static constexpr int TX = 32, TY = S <= 2 ? 16 : 8;  // output pixels
+  static constexpr int NT = n_taps(S), O0 = o_min(S);
+  static constexpr int PC = S * (TX - 1) + NT, PR = S * (TY - 1) + NT;  // staged patch
+};
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void downscale_rgba_kernel(const uint8_t* __restrict__ rgba,
+                                                                  uint8_t* __restrict__ small,
+                                                                  int W, int H, int w, int h,
+                                                                  int tiles_x) {
+  using T = Tile<S>;
+  constexpr int TX = T::TX, TY = T::TY, NT = T::NT, PC = T::PC, PR = T::PR;
+  __shared__ uchar4 s_src[PR][PC];
+  __shared__ float s_h[3][PR][TX + 1];
+  const int tid = threadIdx.x;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int j0 = tx * TX, i0 = ty * TY;
+
+  // clamped fetch of the patch: consecutive lanes consecutive pixels of a row
+  const int sx0 = j0 * S + T::O0, sy0 = i0 * S + T::O0;
+  for (int e = tid; e < PR * PC; e += kThreads) {
+    const int r = e / PC, c = e - r * PC;
+    const int sx = min(max(sx0 + c, 0), W - 1), sy = min(max(sy0 + r, 0), H - 1);
+    s_src[r][c] = reinterpret_cast<const uchar4*>(rgba)[(size_t)sy * W + sx];
+  }
+  __syncthreads();
+
+  // horizontal pass: patch row r, output column x -> one value per channel
+  const int x = tid % TX;
+  for (int r = tid / TX; r < PR; r += kThreads / TX) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const uchar4 p = s_src[r][S * x + t];
+      const float wt = c_down.w[S][t];
+      a0 += wt * (float)p.x;
+      a1 += wt * (float)p.y;
+      a2 += wt * (float)p.z;
+    }
+    s_h[0][r][x] = a0;
+    s_h[1][r][x] = a1;
+    s_h[2][r][x] = a2;
+  }
+  __syncthreads();
+
+  // vertical pass: NT rows per output, round to nearest, alpha 255
+  const int j = j0 + x;
+  if (j >= w) return;
+  for (int y = tid / TX; y < TY; y += kThreads / TX) {
+    const int i = i0 + y;
+    if (i >= h) break;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const float wt = c_down.w[S][t];
+      a0 += wt * s_h[0][S * y + t][x];
+      a1 += wt * s_h[1][S * y + t][x];
+      a2 += wt * s_h[2][S * y + t][x];
+    }
+    auto q = [](float v) { return (uint8_t)floorf(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f); };
+    reinterpret_cast<uchar4*>(small)[(size_t)i * w + j] = make_uchar4(q(a0), q(a1), q(a2), 255);
+  }
+}
+
+// gather_tiles: one workgroup per tile, of any size (nothing of the tile is
+// held on chip: the second pass re-reads the plane, from cache).  The mean is
+// a fixed-order sum that depends on tw x th alone: thread t adds the tile's
+// elements t, t + 256, t + 512, ... (row-major within the tile) in that
+// order, then the 256 partial sums meet in a binary tree: six butterfly
+// levels inside each wave, two more over the four waves' sums in LDS.
+template <bool SUB_MEAN>
+__global__ __launch_bounds__(kThreads) void gather_tiles_kernel(
+    const float* __restrict__ plane, float* __restrict__ tiles, float* __restrict__ means, int pw,
+    int x0, int y0, int stride, int nx, int tw, int th) {
+  __shared__ float s_part[kThreads / 64];
+  const int tid = threadIdx.x;
+  const int iy = blockIdx.x / nx, ix = blockIdx.x - iy * nx;
+  const float* src = plane + (size_t)(y0 + iy * stride) * pw + (x0 + ix * stride);
+  const uint32_t n = (uint32_t)tw * th, utw = tw;  // n <= 2^31-1: e + 256 stays below 2^32
+  float mean = 0.0f;
+  if (SUB_MEAN) {
+    float acc = 0.0f;
+    for (uint32_t e = tid; e < n; e += kThreads) {
+      const uint32_t r = e / utw, c = e - r * utw;
+      acc += src[(size_t)r * pw + c];
+    }
+    // butterfly over the wave's 64 lanes (every lane ends with the same
+    // bits: a + b == b + a), then the four waves' sums as (0 + 1) + (2 + 3)
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) acc += __shfl_xor(acc, k, 64);
+    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+    __syncthreads();
+    mean = ((s_part[0] + s_part[1]) + (s_part[2] + s_part[3])) / (float)n;
+    if (means && tid == 0) means[blockIdx.x] = mean;
+  }
+  float* dst = tiles + (size_t)blockIdx.x * n;
+  for (uint32_t e = tid; e < n; e += kThreads) {
+    const uint32_t r = e / utw, c = e - r * utw;
+    const float v = src[(size_t)r * pw + c];
+    dst[e] = SUB_MEAN ? v - mean : v;
+  }
+}
+
+}  // namespace
+
+int downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H, uint32_t scale,
+                   hipStream_t s) {
+  SRCNN_PROFILE("downscale_rgba", s);
+  const uint32_t w = W / scale, h = H / scale;
+#define SRCNN_DOWN(S)                                                                           \
+  {                                                                                             \
+    const uint32_t tx = (w + Tile<S>::TX - 1) / Tile<S>::TX, ty = (h + Tile<S>::TY - 1) / Tile<S>::TY; \
+    hipLaunchKernelGGL(downscale_rgba_kernel<S>, dim3(tx* ty), dim3(kThreads), 0, s, rgba, small, \
+                       (int)W, (int)H, (int)w, (int)h, (int)tx);                                \
+  }
+  switch (scale) {
+    case 1: SRCNN_DOWN(1); break;
+    case 2: SRCNN_DOWN(2); break;
+    case 3: SRCNN_DOWN(3); break;
+    case 4: SRCNN_DOWN(4); break;
+    default: return fail(SRCNN_ERR_INVALID, "downscale_rgba: scale %u has no kernel", scale);
+  }
+#undef SRCNN_DOWN
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+
+int gather_tiles(const float* plane, uint32_t pw, uint32_t x0, uint32_t y0, uint32_t stride,
+                 uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th, int sub_mean, float* tiles,
+                 float* means, hipStream_t s) {
+  SRCNN_PROFILE("gather_tiles", s);
+  if (sub_mean)
+    hipLaunchKernelGGL(gather_tiles_kernel<true>, dim3(nx * ny), dim3(kThreads), 0, s, plane, tiles,
+                       means, (int)pw, (int)x0, (int)y0, (int)stride, (int)nx, (int)tw, (int)th);
+  else
+    hipLaunchKernelGGL(gather_tiles_kernel<false>, dim3(nx * ny), dim3(kThreads), 0, s, plane, tiles,
+                       means, (int)pw, (int)x0, (int)y0, (int)stride, (int)nx, (int)tw, (int)th);
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+
+int preload_pairs() {
+  const void* k[] = {(const void*)downscale_rgba_kernel<1>, (const void*)downscale_rgba_kernel<2>,
+                     (const void*)downscale_rgba_kernel<3>, (const void*)downscale_rgba_kernel<4>,
+                     (const void*)gather_tiles_kernel<true>, (const void*)gather_tiles_kernel<false>};
+  return resolve_kernels(k, 6);
+}
+
+}  // namespace srcnn

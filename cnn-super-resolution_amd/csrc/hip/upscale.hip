@@ -15,6 +15,7 @@
 // registers.  S is a template parameter: the only divisions left are by that
 // constant, once per output row, and the tile decode once per workgroup.
 #include "common.hpp"
+#include "keys.hpp"
 #include "ops.hpp"
 
 namespace srcnn {
@@ -36,11 +37,7 @@ struct Tile {
   static constexpr int PCP = PC + 1;                                            // its LDS pitch
 };
 
-// Keys cubic, a = -0.5
-constexpr double keys(double x) {
-  x = x < 0 ? -x : x;
-  return x <= 1 ? (1.5 * x - 2.5) * x * x + 1 : x < 2 ? ((-0.5 * x + 2.5) * x - 4) * x + 2 : 0;
-}
+// (keys(): the Keys cubic, a = -0.5, keys.hpp)
 // phase k of scale s: d = (k+0.5)/s - 0.5, b = floor(d) (-1 or 0), t = d - b;
 // taps j+b-1 .. j+b+2 at distances t+1, t, 1-t, 2-t
 constexpr int tap_base(int s, int k) { return 2 * k + 1 < s ? -1 : 0; }

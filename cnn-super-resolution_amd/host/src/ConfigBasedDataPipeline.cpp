@@ -257,6 +257,48 @@ void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, 
 
 // ---------------------------------------------------------------- training
 
+size_t ConfigBasedDataPipeline::make_training_pairs(ImageData& full, unsigned scale, size_t tile,
+                                                    size_t stride,
+                                                    std::vector<SampleAllocationPool>& out) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(scale >= 1 && scale <= 4, "make_training_pairs: scale must be 1, 2, 3 or 4");
+  require(tile > 0 && tile <= 0xffffffffu && stride > 0 && stride <= 0xffffffffu,
+          "make_training_pairs: tile and stride must be > 0");
+  require(full.w > 0 && full.h > 0, "make_training_pairs: empty image");
+  const size_t count = srcnn_make_pairs_count(full.w, full.h, scale, uint32_t(tile), uint32_t(stride),
+                                              nullptr, nullptr);
+  if (count == 0) return 0;
+  const size_t ws = srcnn_make_pairs_workspace_bytes(full.w, full.h, scale);
+  require(ws > 0, std::string("make_training_pairs: ") + srcnn_last_error());
+  const size_t tile_bytes = tile * tile * sizeof(float);
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, full.w, full.h);
+  _context->write_image(rgba, full, true);
+  MemoryHandle X = _context->allocate(srcnn::MEM_READ_WRITE, count * tile_bytes);
+  MemoryHandle T = _context->allocate(srcnn::MEM_READ_WRITE, count * tile_bytes);
+  void* wsp = scratch(ws);
+  if (!_make_pairs_kernel)
+    _make_pairs_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_make_pairs", 0, 0, 0, false,
+                                                 "-D SCALE=" + std::to_string(scale));
+  {
+    srcnn::Context::Launch l(*_context, *_make_pairs_kernel);
+    check(srcnn_make_pairs(static_cast<const uint8_t*>(_context->ptr(rgba)), full.w, full.h, scale,
+                           uint32_t(tile), uint32_t(stride), _context->fptr(X), _context->fptr(T), wsp, ws,
+                           _context->stream()),
+          "make_pairs");
+  }
+  _context->block();  // (the image is released below)
+  _context->raw_memory(rgba)->release();
+  out.reserve(out.size() + count);
+  for (size_t i = 0; i < count; ++i) {
+    SampleAllocationPool s;
+    s.input_luma = _context->view(X, i * tile_bytes, tile_bytes);
+    s.expected_luma = _context->view(T, i * tile_bytes, tile_bytes);
+    s.input_w = s.input_h = tile;
+    out.push_back(s);
+  }
+  return count;
+}
+
 Event ConfigBasedDataPipeline::backpropagate(LayerAllocationPool& l1, LayerAllocationPool& l2,
                                              LayerAllocationPool& l3, size_t w, size_t h, size_t n,
                                              Event* ev) {

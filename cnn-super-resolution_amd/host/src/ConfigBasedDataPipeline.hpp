@@ -112,6 +112,16 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * and reads the RGB result back.  Every output pixel passes through the
    * net: no border frame is left, also with scale 1. */
   void super_resolve(ImageData& low_res, unsigned scale, ImageData& result);
+  /** Training pairs of one full-size image, cut on the device: one
+   * srcnn_make_pairs call (the image degraded by the resampling super_resolve
+   * applies: down by `scale`, bicubic up again; then a grid of tile x tile
+   * windows at `stride`, the input tiles minus their own mean) appends one
+   * sample per tile to `out` and returns their number, 0 if the image is too
+   * small for one tile.  The samples' input_luma / expected_luma are views
+   * into the two batch buffers of the call (never released on their own);
+   * input_w = input_h = tile. */
+  size_t make_training_pairs(ImageData& full, unsigned scale, size_t tile, size_t stride,
+                             std::vector<SampleAllocationPool>& out);
   /** L3 output of the last forward / execute_batch chunk */
   MemoryHandle result_buffer() const { return _out_3_gpu_buf; }
   /** the flat [gW1|gB1|gW2|gB2|gW3|gB3] buffer (gpu_nullptr before training
@@ -178,6 +188,7 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _train_kernel = nullptr;
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
+  Kernel* _make_pairs_kernel = nullptr;
   Kernel* _update_all_kernel = nullptr;
   Kernel* _allreduce_kernel = nullptr;
   MemoryHandle _comm_scalar = gpu_nullptr;

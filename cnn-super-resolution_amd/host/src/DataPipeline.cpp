@@ -199,6 +199,59 @@ Event DataPipeline::upscale_compose(ImageData& img, MemoryHandle org_img, Memory
   return _context->mark();
 }
 
+void DataPipeline::downscale(ImageData& img, unsigned scale, ImageData& out) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(scale >= 1 && scale <= 4, "downscale: scale must be 1, 2, 3 or 4");
+  require(img.w >= int(scale) && img.h >= int(scale), "downscale: image smaller than the scale");
+  const size_t w = size_t(img.w) / scale, h = size_t(img.h) / scale;
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, img.w, img.h);
+  _context->write_image(rgba, img, true);
+  MemoryHandle small = _context->create_image(srcnn::MEM_READ_WRITE, w, h);
+  if (!_downscale_kernel)
+    _downscale_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "downscale_rgba");
+  {
+    srcnn::Context::Launch l(*_context, *_downscale_kernel);
+    check(srcnn_downscale_rgba(static_cast<const uint8_t*>(_context->ptr(rgba)),
+                               static_cast<uint8_t*>(_context->ptr(small)), img.w, img.h, scale,
+                               _context->stream()),
+          "downscale");
+  }
+  out = ImageData(int(w), int(h), 4);
+  _context->read_buffer(small, 0, out.data.size(), out.data.data(), true);
+  _context->raw_memory(small)->release();
+  _context->raw_memory(rgba)->release();
+}
+
+Event DataPipeline::gather_tiles(MemoryHandle plane, size_t pw, size_t ph, size_t x0, size_t y0,
+                                 size_t stride, size_t nx, size_t ny, size_t tw, size_t th,
+                                 bool sub_mean, MemoryHandle& tiles, MemoryHandle* means, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  const size_t lim = 0xffffffffu;
+  require(pw <= lim && ph <= lim && x0 <= lim && y0 <= lim && stride <= lim && nx <= lim && ny <= lim &&
+              tw <= lim && th <= lim,
+          "gather_tiles: argument beyond 32 bits");
+  if (!SRCNN_HAS_SIZE(plane, pw * ph * sizeof(float)))
+    throw std::runtime_error("Invalid size of the plane buffer");
+  _context->wait(ev);
+  const size_t n = nx * ny;
+  if (!SRCNN_HAS_SIZE(tiles, n * tw * th * sizeof(float)))
+    tiles = _context->allocate(srcnn::MEM_READ_WRITE, std::max<size_t>(n * tw * th, 1) * sizeof(float));
+  float* mp = nullptr;
+  if (means && sub_mean) {
+    if (!SRCNN_HAS_SIZE(*means, n * sizeof(float)))
+      *means = _context->allocate(srcnn::MEM_READ_WRITE, std::max<size_t>(n, 1) * sizeof(float));
+    mp = _context->fptr(*means);
+  }
+  if (!_gather_tiles_kernel)
+    _gather_tiles_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "gather_tiles");
+  srcnn::Context::Launch l(*_context, *_gather_tiles_kernel);
+  check(srcnn_gather_tiles(_context->fptr(plane), uint32_t(pw), uint32_t(ph), uint32_t(x0), uint32_t(y0),
+                           uint32_t(stride), uint32_t(nx), uint32_t(ny), uint32_t(tw), uint32_t(th),
+                           sub_mean ? 1 : 0, _context->fptr(tiles), mp, _context->stream()),
+        "gather_tiles");
+  return _context->mark();
+}
+
 float DataPipeline::sum(MemoryHandle data, bool squared, Event* ev) {
   check_initialized(LOAD_KERNEL_MISC);
   _context->wait(ev);

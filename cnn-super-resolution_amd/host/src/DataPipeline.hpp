@@ -70,6 +70,19 @@ class DataPipeline {
   Event upscale_compose(ImageData&, MemoryHandle gpu_buf_org_img, MemoryHandle gpu_buf_new_luma,
                         MemoryHandle& target, size_t scale, Event* ev = nullptr);
 
+  /** Extension, the inverse of the upscale: `img` antialiased-bicubic
+   * downscaled by `scale` (1..4) on the device into `out`, RGBA of
+   * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
+  void downscale(ImageData& img, unsigned scale, ImageData& out);
+
+  /** Extension: cut nx x ny tiles of tw x th floats, tile (ix, iy) from
+   * (x0 + ix*stride, y0 + iy*stride), out of the plane_w x plane_h float plane
+   * into `tiles` ([nx*ny][th][tw]), each minus its own mean when sub_mean;
+   * `means` (optional) then receives the nx*ny means (srcnn_gather_tiles). */
+  Event gather_tiles(MemoryHandle plane, size_t plane_w, size_t plane_h, size_t x0, size_t y0,
+                     size_t stride, size_t nx, size_t ny, size_t tw, size_t th, bool sub_mean,
+                     MemoryHandle& tiles, MemoryHandle* means = nullptr, Event* ev = nullptr);
+
   /** Forward of one layer over `sample_count` samples (reference :358-410). */
   Event execute_layer(Kernel&, const LayerData&, LayerAllocationPool&, MemoryHandle& gpu_buf_in,
                       size_t input_w, size_t input_h, size_t sample_count,
@@ -141,6 +154,8 @@ class DataPipeline {
   Kernel* _swap_luma_kernel = nullptr;
   Kernel* _upscale_luma_kernel = nullptr;
   Kernel* _upscale_compose_kernel = nullptr;
+  Kernel* _downscale_kernel = nullptr;
+  Kernel* _gather_tiles_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;
   Kernel* _sum_squared_kernel = nullptr;

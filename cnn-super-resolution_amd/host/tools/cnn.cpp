@@ -1,9 +1,10 @@
 // cnn -- the command line of the reference (src/Main_cl.cpp) on the MI355X
 // pipeline:
 //
-//   cnn [-h] [train | upscale] [dry] [profile] -c CONFIG -i IN [-o OUT]
+//   cnn [-h] [train | upscale | downscale] [dry] [profile] -c CONFIG -i IN [-o OUT]
 //       [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]
 //       [--validation-percent P] [--mini-batches M] [--save-momentum]
+//       [--from-images] [--tile N] [--stride N]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -13,9 +14,18 @@
 //           net and the composition all run on the device (srcnn_upscale), and
 //           every output pixel passes through the net.  --scale 1 is the
 //           "same size, no border frame" mode for inputs that are already scaled.
+// downscale: (extension) IN is a full-size image, OUT the image of 1/S the
+//           size (RGB), resampled on the device by the inverse of the upscale
+//           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
+//           for `cnn upscale`.  Needs no CONFIG.
 // train:    IN is a directory of <name>_large.<ext> / <name>_small.<ext> pairs
 //           (ground truth / degraded input, tools/make_samples.py makes
 //           them), OUT the parameters.json written at the end.
+//           With --from-images (extension) IN is a directory of full-size
+//           images; each is cut on the device into --tile x --tile pairs at
+//           --stride (defaults 33 and 14, the paper's sub-image size and
+//           stride), the input tiles degraded by exactly what `cnn upscale
+//           --scale S` applies at inference (srcnn_make_pairs).
 // Differences from the reference, on purpose: paths are joined with '/'
 // (the reference hard-codes "\\", src/Main_cl.cpp:284-287), the epoch
 // shuffle is seeded (--seed; the reference uses unseeded rand()).
@@ -57,9 +67,12 @@ using namespace cnn_sr;
 namespace {
 
 struct Args {
-  bool train = false, upscale = false, dry = false, profile = false, help = false, version = false;
-  unsigned scale = 2;      // upscale: --scale
+  bool train = false, upscale = false, downscale = false, dry = false, profile = false, help = false, version = false;
+  unsigned scale = 2;      // upscale, downscale, train --from-images: --scale
   bool scale_set = false;
+  bool from_images = false;  // train --from-images: cut the pairs on the device
+  size_t tile = 33, stride = 14;
+  bool tile_set = false, stride_set = false;
   std::string config, in, out;
   size_t epochs = 0;
   uint64_t seed = 0;
@@ -76,15 +89,19 @@ struct Args {
 
 void usage() {
   std::cout
-      << "usage: cnn [-h] [train | upscale] [dry] [profile] -c CONFIG -i IN [-o OUT]\n"
+      << "usage: cnn [-h] [train | upscale | downscale] [dry] [profile] -c CONFIG -i IN [-o OUT]\n"
          "           [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]\n"
-         "           [--validation-percent P] [--mini-batches M] [--save-momentum]\n\n"
+         "           [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
+         "           [--from-images] [--tile N] [--stride N]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
          "  upscale               upscale mode: IN is a low-resolution image, OUT the image\n"
          "                        of --scale times the size (bicubic + net on the device;\n"
          "                        no un-enhanced border frame)\n"
+         "  downscale             downscale mode: IN is a full-size image, OUT the image of\n"
+         "                        1 / --scale the size (the inverse of the upscale mode's\n"
+         "                        bicubic, on the device; -c is not needed)\n"
          "  dry                   do not store the result\n"
          "  profile               print kernel execution times\n"
          "  -c, --config CONFIG   CNN configuration (config.json)\n"
@@ -92,8 +109,14 @@ void usage() {
          "                        training\n"
          "  -o, --out OUT         output path (result image or new parameters file)\n"
          "  -e, --epochs EPOCHS   number of epochs during training\n"
-         "  --scale S             upscale factor 1, 2, 3 or 4 (default 2; upscale mode only;\n"
-         "                        1: same size, every pixel through the net)\n"
+         "  --scale S             scale factor 1, 2, 3 or 4 (default 2; upscale, downscale\n"
+         "                        and train --from-images only; upscale 1: same size, every\n"
+         "                        pixel through the net)\n"
+         "  --from-images         train: IN is a directory of full-size images; the sample\n"
+         "                        pairs are cut on the device, the inputs degraded by\n"
+         "                        --scale as the upscale mode resamples\n"
+         "  --tile N              --from-images: sample size (default 33)\n"
+         "  --stride N            --from-images: step between samples (default 14)\n"
          "  --seed N              seed of the random parameters and the epoch shuffles\n"
          "  --device D            HIP device index (default 0)\n"
          "  --devices N           train data-parallel on devices D .. D+N-1 (default 1)\n"
@@ -117,6 +140,22 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "--version") a.version = true;
     else if (s == "train") a.train = true;
     else if (s == "upscale") a.upscale = true;
+    else if (s == "downscale") a.downscale = true;
+    else if (s == "--from-images") a.from_images = true;
+    else if (s == "--tile" || s == "--stride") {
+      const std::string v = value(s.c_str());
+      size_t n = 0;
+      try {
+        size_t used = 0;
+        n = std::stoul(v, &used);
+        if (used != v.size() || v[0] == '-') n = 0;
+      } catch (const std::exception&) {
+        n = 0;
+      }
+      if (n == 0 || n > 0xffffffffu) throw std::runtime_error(s + " must be a positive integer");
+      (s == "--tile" ? a.tile : a.stride) = n;
+      (s == "--tile" ? a.tile_set : a.stride_set) = true;
+    }
     else if (s == "--scale") {
       const std::string v = value("--scale");
       if (v != "1" && v != "2" && v != "3" && v != "4")
@@ -145,9 +184,18 @@ bool parse(int argc, char** argv, Args& a) {
     else throw std::runtime_error("unknown argument '" + s + "'");
   }
   if (a.help || a.version) return false;
-  if (a.scale_set && !a.upscale) throw std::runtime_error("--scale needs the upscale mode");
-  if (a.upscale && a.train) throw std::runtime_error("train and upscale are different modes");
-  if (a.config.empty() || a.in.empty()) throw std::runtime_error("--config and --in are required");
+  if (int(a.upscale) + int(a.train) + int(a.downscale) > 1)
+    throw std::runtime_error("train, upscale and downscale are different modes");
+  if (a.from_images && !a.train) throw std::runtime_error("--from-images needs the train mode");
+  if ((a.tile_set || a.stride_set) && !a.from_images)
+    throw std::runtime_error("--tile and --stride need train --from-images");
+  if (a.scale_set && !a.upscale && !a.downscale && !a.from_images)
+    throw std::runtime_error("--scale needs the upscale mode, the downscale mode or train --from-images");
+  if (a.downscale) {
+    if (a.in.empty()) throw std::runtime_error("--in is required");
+  } else if (a.config.empty() || a.in.empty()) {
+    throw std::runtime_error("--config and --in are required");
+  }
   if (a.devices < 1) throw std::runtime_error("--devices must be >= 1");
   if (a.same_device && !a.host_exchange)
     throw std::runtime_error("--same-device needs --exchange host (RCCL takes one rank per device)");
@@ -220,6 +268,59 @@ int upscale(ConfigBasedDataPipeline& p, const Args& a) {
   return 0;
 }
 
+/** `cnn downscale`: the full-size image through srcnn_downscale_rgba */
+int downscale(DataPipeline& p, const Args& a) {
+  ImageData img, small;
+  srcnn::image::load(a.in, img, 4);
+  srcnn::require(img.w >= int(a.scale) && img.h >= int(a.scale),
+                 "image " + std::to_string(img.w) + "x" + std::to_string(img.h) + " is smaller than the scale");
+  p.downscale(img, a.scale, small);
+  if (!a.dry && !a.out.empty()) {
+    ImageData rgb(small.w, small.h, 3);
+    for (size_t i = 0, n = size_t(small.w) * small.h; i < n; ++i)
+      for (int c = 0; c < 3; ++c) rgb.data[3 * i + c] = small.data[4 * i + c];
+    std::cout << "Saving result image to: '" << a.out << "'" << std::endl;
+    srcnn::image::write(a.out.c_str(), rgb);
+  }
+  p.context()->block();
+  return 0;
+}
+
+/** `train --from-images`: every file of the directory that decodes, in name
+ * order, cut into sample pairs on the device (one srcnn_make_pairs call per
+ * image) */
+void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
+                       std::vector<SampleAllocationPool>& samples) {
+  DIR* d = opendir(a.in.c_str());
+  if (!d) throw srcnn::IOException("cannot open images directory '" + a.in + "'");
+  std::vector<std::string> names;
+  while (dirent* e = readdir(d)) {
+    std::string f = e->d_name;
+    if (f != "." && f != "..") names.push_back(f);
+  }
+  closedir(d);
+  std::sort(names.begin(), names.end());
+  size_t images = 0;
+  for (auto& f : names) {
+    ImageData img;
+    try {
+      srcnn::image::load(a.in + "/" + f, img, 4);
+    } catch (const std::exception& e) {
+      if (lead) std::cout << "'" << f << "' does not decode (" << e.what() << "). Skipping image" << std::endl;
+      continue;
+    }
+    const size_t n = p.make_training_pairs(img, a.scale, a.tile, a.stride, samples);
+    if (n == 0) {
+      if (lead)
+        std::cout << "'" << f << "' (" << img.w << "x" << img.h << ") is too small for one " << a.tile << "x"
+                  << a.tile << " tile at scale " << a.scale << ". Skipping image" << std::endl;
+      continue;
+    }
+    ++images;
+  }
+  if (lead) std::cout << "created " << samples.size() << " sample pairs from " << images << " images" << std::endl;
+}
+
 /** Contiguous slice [start, start + count) of n items for `rank` of `world`
  * (the remainder goes to the lowest ranks; srcnn_amd/parallel.py shard). */
 std::pair<size_t, size_t> shard(size_t n, int rank, int world) {
@@ -236,20 +337,23 @@ int train(ConfigBasedDataPipeline& p, const Args& a, uint64_t shuffle_seed, Grad
           int rank = 0, int world = 1) {
   auto& ctx = *p.context();
   const bool lead = rank == 0;
-  auto files = training_samples(a.in);
-  if (files.empty()) throw std::runtime_error("no training samples in '" + a.in + "'");
-  const size_t nval = files.size() * a.validation_percent / 100, ntrain = files.size() - nval;
+  GpuAllocationPool pools;
+  std::vector<std::pair<std::string, std::string>> files;
+  if (a.from_images) pairs_from_images(p, a, lead, pools.samples);
+  else files = training_samples(a.in);
+  const size_t total = a.from_images ? pools.samples.size() : files.size();
+  if (total == 0) throw std::runtime_error("no training samples in '" + a.in + "'");
+  const size_t nval = total * a.validation_percent / 100, ntrain = total - nval;
   if (lead) {
     if (nval == 0) std::cout << "[WARNING] Validation set is empty" << std::endl;
     else
-      std::cout << "validation_set_size: " << nval << "/" << files.size() << " = "
-                << (nval * 100.0f / files.size()) << "%" << std::endl;
+      std::cout << "validation_set_size: " << nval << "/" << total << " = "
+                << (nval * 100.0f / total) << "%" << std::endl;
   }
   srcnn::require(ntrain > 0, "Training set is empty");
   const size_t my_train = shard(ntrain, rank, world).second;
   p.set_mini_batch_size(std::max<size_t>(my_train, 1) / a.mini_batches + a.mini_batches);  // src/Main_cl.cpp:128-129
 
-  GpuAllocationPool pools;
   for (auto& f : files) {
     ImageData large, small;
     SampleAllocationPool s;
@@ -482,7 +586,15 @@ int main(int argc, char** argv) {
     std::cout << "!!! RUNNING IN PROFILING MODE !!!" << std::endl;
   if (a.train)
     std::cout << "Training mode, epochs: " << a.epochs << std::endl
-              << "Training samples directory: " << a.in << std::endl
+              << (a.from_images ? "Full-size images directory (pairs cut on the device, scale " +
+                                      std::to_string(a.scale) + ", tile " + std::to_string(a.tile) +
+                                      ", stride " + std::to_string(a.stride) + "): "
+                                : std::string("Training samples directory: "))
+              << a.in << std::endl
+              << "Output: " << (a.dry ? "-" : a.out) << std::endl;
+  else if (a.downscale)
+    std::cout << "Downscale mode, scale: " << a.scale << std::endl
+              << "Input image: " << a.in << std::endl
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   else if (a.upscale)
     std::cout << "Upscale mode, scale: " << a.scale << std::endl
@@ -493,6 +605,13 @@ int main(int argc, char** argv) {
               << "Input image: " << a.in << std::endl
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   try {
+    if (a.downscale) {
+      srcnn::Context context;
+      context.init(a.profile, a.device);
+      DataPipeline pipeline(&context);
+      pipeline.init(DataPipeline::LOAD_KERNEL_LUMA);
+      return downscale(pipeline, a);
+    }
     ConfigReader reader;
     Config cfg = reader.read(a.config.c_str());
     std::cout << cfg << std::endl;

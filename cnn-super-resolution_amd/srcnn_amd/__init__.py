@@ -84,6 +84,11 @@ SIGNATURES = {
     "srcnn_swap_luma": (_I, [_P, _P, _P, _U, _U, _U, _U, _P]),
     "srcnn_upscale_luma": (_I, [_P, _P, _U, _U, _U, _U, _P]),
     "srcnn_upscale_compose": (_I, [_P, _P, _P, _U, _U, _U, _P]),
+    "srcnn_downscale_rgba": (_I, [_P, _P, _U, _U, _U, _P]),
+    "srcnn_gather_tiles": (_I, [_P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _I, _P, _P, _P]),
+    "srcnn_make_pairs_count": (_S, [_U, _U, _U, _U, _U, ctypes.POINTER(_U), ctypes.POINTER(_U)]),
+    "srcnn_make_pairs_workspace_bytes": (_S, [_U, _U, _U]),
+    "srcnn_make_pairs": (_I, [_P, _U, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
@@ -319,6 +324,40 @@ def upscale_compose(rgba, new_luma, rgb, w, h, scale, s=None):
     """bicubic x scale of the source's r, g, b + new_luma [scale*h][scale*w]
     -> rgb [scale*h][scale*w][3] u8 (srcnn_upscale_compose)."""
     _call("srcnn_upscale_compose", ptr(rgba), ptr(new_luma), ptr(rgb), w, h, scale, s)
+
+
+def downscale_rgba(rgba, small, W, H, scale, s=None):
+    """rgba [H][W][4] u8 -> antialiased bicubic / scale, small
+    [H//scale][W//scale][4] u8, alpha 255 (srcnn_downscale_rgba)."""
+    _call("srcnn_downscale_rgba", ptr(rgba), ptr(small), W, H, scale, s)
+
+
+def gather_tiles(plane, pw, ph, x0, y0, stride, nx, ny, tw, th, sub_mean, tiles, means=None, s=None):
+    """plane [ph][pw] f32 -> tiles [nx*ny][th][tw], tile iy*nx + ix from
+    (x0 + ix*stride, y0 + iy*stride); with sub_mean each minus its own mean,
+    which means [nx*ny] (may be None) then receives (srcnn_gather_tiles)."""
+    _call("srcnn_gather_tiles", ptr(plane), pw, ph, x0, y0, stride, nx, ny, tw, th, int(sub_mean),
+          ptr(tiles), ptr(means), s)
+
+
+def make_pairs_count(W, H, scale, tile, stride):
+    """(count, nx, ny) of the tile grid srcnn_make_pairs cuts; count 0 if the
+    image is too small or an argument is invalid."""
+    nx, ny = _U(), _U()
+    n = _lib.srcnn_make_pairs_count(W, H, scale, tile, stride, ctypes.byref(nx), ctypes.byref(ny))
+    return n, nx.value, ny.value
+
+
+def make_pairs_workspace_bytes(W, H, scale):
+    return _lib.srcnn_make_pairs_workspace_bytes(W, H, scale)
+
+
+def make_pairs(rgba, W, H, scale, tile, stride, X, T, ws, ws_bytes, s=None):
+    """Full-size rgba [H][W][4] u8 -> X, T [count][tile][tile] f32
+    (srcnn_make_pairs): downscale_rgba, upscale_luma (pad 0), extract_luma,
+    gather_tiles with the mean (X) and without (T)."""
+    _call("srcnn_make_pairs", ptr(rgba), W, H, scale, tile, stride, ptr(X), ptr(T), ptr(ws),
+          ws_bytes, s)
 
 
 # ---- network level ----

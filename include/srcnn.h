@@ -204,6 +204,68 @@ SRCNN_API int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, 
                                     uint32_t w, uint32_t h, uint32_t scale,
                                     srcnn_stream_t stream);
 
+/* Training pairs from a full-size image, on the device (an MI355X extension;
+ * the reference's pairs are made on the host, one file per sample).  The
+ * training-side mirror of the upscaling front end: DESIGN.md 11.1 is the spec.
+ *
+ * srcnn_downscale_rgba: rgba [H][W][4] u8 -> small [H/s][W/s][4] u8 (integer
+ * division; s = 1, 2, 3 or 4; W >= s, H >= s): the antialiased Keys bicubic
+ * (a = -0.5, stretched by s) at half-pixel centres, source indices clamped to
+ * the image, separable, fp32, horizontal pass first, rounded to nearest;
+ * alpha = 255.  The trailing W - s*(W/s) columns and H - s*(H/s) rows have no
+ * output pixel of their own but are tap sources.  With s = 1 the r, g, b bytes
+ * are the source's.  Downscaling by s and srcnn_upscale_luma by s are aligned:
+ * no shift between them.
+ *
+ * srcnn_gather_tiles: plane [ph][pw] f32 -> tiles [nx*ny][th][tw] f32; tile
+ * i = iy*nx + ix is the window at (x0 + ix*stride, y0 + iy*stride).  With
+ * sub_mean != 0 each tile has its own mean subtracted (srcnn_sub_mean per
+ * sample): a fixed-order fp32 sum that depends on tw x th alone -- not on the
+ * grid, the neighbouring tiles or what lies around the buffers -- divided by
+ * (float)(tw*th); means (device, may be NULL) [nx*ny] then gets each tile's
+ * mean.  With sub_mean == 0 the tiles are copies and means is not touched.
+ * Writes exactly the nx*ny*th*tw floats of tiles (and the nx*ny of means).
+ *
+ * SRCNN_ERR_INVALID, before any launch: scale outside 1..4; W < s or H < s;
+ * stride, nx, ny, tw or th zero; a grid that leaves the plane (x0 +
+ * (nx-1)*stride + tw > pw, likewise in y); a null buffer; or a size beyond the
+ * kernels' 32-bit index: the source's pixels W*H, the plane's floats pw*ph and
+ * the tile count nx*ny must each number at most 2^31-1. */
+SRCNN_API int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
+                                   uint32_t scale, srcnn_stream_t stream);
+SRCNN_API int srcnn_gather_tiles(const float* plane, uint32_t pw, uint32_t ph, uint32_t x0,
+                                 uint32_t y0, uint32_t stride, uint32_t nx, uint32_t ny,
+                                 uint32_t tw, uint32_t th, int sub_mean, float* tiles,
+                                 float* means, srcnn_stream_t stream);
+
+/* One full-size image -> the (X, T) tile batches srcnn_train_fwd_bwd reads:
+ * X [count][tile][tile] = the image degraded by exactly the resampling the
+ * inference path applies (down by s, then srcnn_upscale_luma by s), each tile
+ * minus its own mean; T [count][tile][tile] = the image's own luma.  The grid:
+ * Wc = s*(W/s), Hc = s*(H/s); nx = (Wc-tile)/stride + 1, ny likewise, origin
+ * (0, 0), tile i = iy*nx + ix.  srcnn_make_pairs_count returns count = nx*ny
+ * (nx, ny may be NULL), 0 if the image is too small for one tile or an
+ * argument is invalid.
+ *
+ * Byte-identical to srcnn_downscale_rgba -> srcnn_upscale_luma(small, W/s,
+ * H/s, s, pad = 0) into the X plane [Hc][Wc] -> srcnn_extract_luma(rgba,
+ * normalize) into the T plane [H][W] -> srcnn_gather_tiles(X plane, sub_mean =
+ * 1) -> srcnn_gather_tiles(T plane, sub_mean = 0): five launches per image.
+ * Stream-ordered, no host synchronisation, no allocation.  `ws` holds the
+ * low-resolution image and the two planes (each 256-byte aligned) under the
+ * memory contract at srcnn_train_workspace_bytes; the call writes every one of
+ * the count*tile*tile floats of X and of T.  srcnn_make_pairs_workspace_bytes
+ * returns 0 for an invalid scale or size.  Errors as srcnn_downscale_rgba and
+ * srcnn_gather_tiles (tile or stride zero, count zero), with srcnn_upscale_luma's
+ * limit on the cropped size (3*Wc*Hc at most 2^31-1), plus SRCNN_ERR_WORKSPACE for a
+ * workspace that is too small. */
+SRCNN_API size_t srcnn_make_pairs_count(uint32_t W, uint32_t H, uint32_t scale, uint32_t tile,
+                                        uint32_t stride, uint32_t* nx, uint32_t* ny);
+SRCNN_API size_t srcnn_make_pairs_workspace_bytes(uint32_t W, uint32_t H, uint32_t scale);
+SRCNN_API int srcnn_make_pairs(const uint8_t* rgba, uint32_t W, uint32_t H, uint32_t scale,
+                               uint32_t tile, uint32_t stride, float* X, float* T, void* ws,
+                               size_t ws_bytes, srcnn_stream_t stream);
+
 /* ---- network level: ConfigBasedDataPipeline (src/ConfigBasedDataPipeline.cpp) ---- */
 typedef struct srcnn_net {
   uint32_t n1, n2, f1, f2, f3; /* Config n1,n2,f1,f2,f3 (src/Config.hpp:27-28) */
@@ -211,7 +273,7 @@ typedef struct srcnn_net {
 
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
  * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale) launch
- * for this net.
+ * for this net, and the kernels of srcnn_make_pairs.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -239,7 +301,8 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     extent of its outputs (grads: srcnn_net_param_count floats; sq_err: one
  *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
  *     A3 extent; srcnn_train_activations: the three extents it documents;
- *     rgb: 3*W*H bytes);
+ *     rgb: 3*W*H bytes; srcnn_make_pairs: count*tile*tile floats of X and of
+ *     T each);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
