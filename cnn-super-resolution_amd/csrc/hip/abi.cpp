@@ -145,6 +145,42 @@ int pair_ws(const char* who, uint32_t W, uint32_t H, uint32_t scale, PairWs* L) 
   return SRCNN_OK;
 }
 
+// srcnn_quality / srcnn_evaluate: the shaved window against the 11 x 11 SSIM
+// window and against what quality_tiles_kernel can index (int coordinates)
+struct QualityDims {
+  uint32_t Ws, Hs;
+  size_t partial_bytes;  // two doubles per workgroup
+};
+bool known_format(int fmt) {
+  return fmt == SRCNN_PIX_LUMA_F32 || fmt == SRCNN_PIX_RGB8 || fmt == SRCNN_PIX_RGBA8;
+}
+int quality_dims(const char* who, uint32_t W, uint32_t H, uint32_t shave, QualityDims* d) {
+  SRCNN_REQUIRE(2 * (uint64_t)shave + 11 <= W && 2 * (uint64_t)shave + 11 <= H,
+                "%s: image %ux%u with %u pixels shaved per side is smaller than the 11x11 window",
+                who, W, H, shave);
+  SRCNN_REQUIRE((uint64_t)W * H <= 0x7fffffffull,
+                "%s: %ux%u exceeds the kernels' 32-bit index: the pixels must number at most 2^31-1",
+                who, W, H);
+  d->Ws = W - 2 * shave;
+  d->Hs = H - 2 * shave;
+  d->partial_bytes = (size_t)srcnn::quality_tile_count(d->Ws, d->Hs) * 2 * sizeof(double);
+  return SRCNN_OK;
+}
+// one image of srcnn_quality: format, pitch, base
+int quality_image(const char* who, const void* p, int fmt, uint32_t pitch, uint32_t W, uint32_t H) {
+  SRCNN_REQUIRE(known_format(fmt), "quality: image %s has unknown pixel format %d", who, fmt);
+  SRCNN_REQUIRE(pitch >= W, "quality: image %s has pitch %u < width %u", who, pitch, W);
+  SRCNN_REQUIRE(p, "quality: null buffer (image %s)", who);
+  SRCNN_REQUIRE(fmt == SRCNN_PIX_RGB8 || ((uintptr_t)p & 3) == 0,
+                "quality: image %s (format %d) is not 4-byte aligned", who, fmt);
+  SRCNN_REQUIRE((uint64_t)pitch * H <= 0x7fffffffull,
+                "quality: image %s, pitch %u x %u rows, exceeds the kernels' 32-bit index: the "
+                "pixels must number at most 2^31-1",
+                who, pitch, H);
+  return SRCNN_OK;
+}
+size_t pixel_bytes(int fmt) { return fmt == SRCNN_PIX_RGB8 ? 3 : 4; }
+
 size_t grad_ws_bytes(uint32_t n_prev, uint32_t n_cur, uint32_t f, uint32_t ow, uint32_t oh,
                      uint32_t batch) {
   size_t b = 0;
@@ -387,6 +423,31 @@ int srcnn_make_pairs(const uint8_t* rgba, uint32_t W, uint32_t H, uint32_t scale
   return srcnn_gather_tiles(tplane, W, H, 0, 0, stride, nx, ny, tile, tile, 0, T, nullptr, stream);
 }
 
+size_t srcnn_quality_workspace_bytes(uint32_t W, uint32_t H, uint32_t shave) {
+  QualityDims d;
+  return quality_dims("quality", W, H, shave, &d) ? 0 : align_up(d.partial_bytes);
+}
+
+int srcnn_quality(const void* a, int fmt_a, uint32_t pitch_a, const void* b, int fmt_b,
+                  uint32_t pitch_b, uint32_t W, uint32_t H, uint32_t shave, double* result,
+                  void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  QualityDims d;
+  if (int rc = quality_dims("quality", W, H, shave, &d)) return rc;
+  if (int rc = quality_image("a", a, fmt_a, pitch_a, W, H)) return rc;
+  if (int rc = quality_image("b", b, fmt_b, pitch_b, W, H)) return rc;
+  SRCNN_REQUIRE(result && ws, "quality: null buffer");
+  SRCNN_REQUIRE((((uintptr_t)result | (uintptr_t)ws) & 7) == 0,
+                "quality: result and workspace hold doubles and must be 8-byte aligned");
+  if (ws_bytes < align_up(d.partial_bytes))
+    return fail(SRCNN_ERR_WORKSPACE, "quality: workspace %zu B < %zu B", ws_bytes,
+                align_up(d.partial_bytes));
+  // the shaved window is a pointer offset: the kernels see Ws x Hs alone
+  const char* pa = static_cast<const char*>(a) + ((size_t)shave * pitch_a + shave) * pixel_bytes(fmt_a);
+  const char* pb = static_cast<const char*>(b) + ((size_t)shave * pitch_b + shave) * pixel_bytes(fmt_b);
+  return srcnn::quality(pa, fmt_a, pitch_a, pb, fmt_b, pitch_b, d.Ws, d.Hs, result,
+                        static_cast<double*>(ws), as_stream(stream));
+}
+
 // ---------------------------------------------------------------------------
 // network level
 // ---------------------------------------------------------------------------
@@ -413,7 +474,7 @@ int srcnn_preload(const srcnn_net* net) {
   int rc;
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
       (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0 ||
-      (rc = srcnn::preload_pairs()) < 0)
+      (rc = srcnn::preload_pairs()) < 0 || (rc = srcnn::preload_quality()) < 0)
     return rc;
   return srcnn::preload_update();
 }
@@ -793,6 +854,74 @@ int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_
   if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
     return rc;
   return srcnn_upscale_compose(rgba, out, rgb, w, h, scale, stream);
+}
+
+// regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |
+// luma plane [Hc][Wc] | srcnn_upscale's workspace | srcnn_quality's, each
+// 256-byte aligned
+struct EvalWs {
+  uint32_t w, h, Wc, Hc;
+  size_t small, rgb, plane, up, q, total;  // byte offsets of the regions, and their sum
+  size_t up_bytes, q_bytes;                // what the upscale and the metric are given
+};
+// every check of the six calls that does not need the buffers; shave < 0: the
+// sizes alone (the workspace query: the metric's workspace does not depend on
+// the shave, it is sized for shave = 0)
+static int eval_ws(const srcnn_net* net, uint32_t W, uint32_t H, uint32_t scale, int64_t shave,
+                   EvalWs* L) {
+  SRCNN_REQUIRE(net, "evaluate: null srcnn_net");
+  if (int rc = down_dims("evaluate", W, H, scale)) return rc;
+  L->w = W / scale;
+  L->h = H / scale;
+  L->up_bytes = srcnn_upscale_workspace_bytes(net, L->w, L->h, scale);
+  if (L->up_bytes == 0) return SRCNN_ERR_INVALID;  // (message from net_dims / up_dims)
+  L->Wc = L->w * scale;
+  L->Hc = L->h * scale;
+  QualityDims q;
+  if (int rc = quality_dims("evaluate", L->Wc, L->Hc, shave < 0 ? 0 : (uint32_t)shave, &q)) return rc;
+  L->q_bytes = srcnn_quality_workspace_bytes(L->Wc, L->Hc, 0);
+  L->small = 0;
+  L->rgb = L->small + align_up((size_t)L->w * L->h * 4);
+  L->plane = L->rgb + align_up((size_t)L->Wc * L->Hc * 3);
+  L->up = L->plane + align_up((size_t)L->Wc * L->Hc * sizeof(float));
+  L->q = L->up + align_up(L->up_bytes);
+  L->total = L->q + align_up(L->q_bytes);
+  return SRCNN_OK;
+}
+
+size_t srcnn_evaluate_workspace_bytes(const srcnn_net* net, uint32_t W, uint32_t H,
+                                      uint32_t scale) {
+  EvalWs L;
+  return eval_ws(net, W, H, scale, -1, &L) ? 0 : L.total;
+}
+
+int srcnn_evaluate(const srcnn_net* net, const uint8_t* rgba, uint32_t W, uint32_t H,
+                   uint32_t scale, uint32_t shave, const float* params, double* result, void* ws,
+                   size_t ws_bytes, srcnn_stream_t stream) {
+  EvalWs L;
+  if (int rc = eval_ws(net, W, H, scale, shave, &L)) return rc;
+  SRCNN_REQUIRE(rgba && params && result && ws, "evaluate: null buffer");
+  SRCNN_REQUIRE((((uintptr_t)rgba & 3) | (((uintptr_t)result | (uintptr_t)ws) & 7)) == 0,
+                "evaluate: rgba must be 4-byte, result and workspace 8-byte aligned");
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "evaluate: workspace %zu B < %zu B", ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  uint8_t* small = reinterpret_cast<uint8_t*>(p + L.small);
+  uint8_t* rgb = reinterpret_cast<uint8_t*>(p + L.rgb);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  int rc;
+  if ((rc = srcnn_downscale_rgba(rgba, small, W, H, scale, stream))) return rc;
+  // the net's result against the truth's top-left Wc x Hc pixels (pitch W)
+  if ((rc = srcnn_upscale(net, small, L.w, L.h, scale, params, rgb, p + L.up, L.up_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_quality(rgb, SRCNN_PIX_RGB8, L.Wc, rgba, SRCNN_PIX_RGBA8, W, L.Wc, L.Hc, shave,
+                          result, p + L.q, L.q_bytes, stream)))
+    return rc;
+  // plain bicubic: the same resampling without the net
+  if ((rc = srcnn_upscale_luma(small, plane, L.w, L.h, scale, 0, stream))) return rc;
+  if ((rc = srcnn_upscale_compose(small, plane, rgb, L.w, L.h, scale, stream))) return rc;
+  return srcnn_quality(rgb, SRCNN_PIX_RGB8, L.Wc, rgba, SRCNN_PIX_RGBA8, W, L.Wc, L.Hc, shave,
+                       result + 3, p + L.q, L.q_bytes, stream);
 }
 
 }  // extern "C"

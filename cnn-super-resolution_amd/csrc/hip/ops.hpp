@@ -234,5 +234,13 @@ int gather_tiles(const float* plane, uint32_t pw, uint32_t x0, uint32_t y0, uint
                  uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th, int sub_mean, float* tiles,
                  float* means, hipStream_t s);
 int preload_pairs();
+// quality.hip: {mse, psnr, ssim} of the luma of two Ws x Hs windows (a, b: the
+// window's first pixel; SRCNN_PIX_* formats; pitches in pixels) into result
+// [3]; partial: 2 * quality_tile_count(Ws, Hs) doubles of scratch
+// (DESIGN.md 12).  Ws, Hs >= 11.
+uint64_t quality_tile_count(uint32_t Ws, uint32_t Hs);
+int quality(const void* a, int fmt_a, uint32_t pitch_a, const void* b, int fmt_b, uint32_t pitch_b,
+            uint32_t Ws, uint32_t Hs, double* result, double* partial, hipStream_t s);
+int preload_quality();
 
 }  // namespace srcnn

@@ -16,6 +16,7 @@
 // constant, once per output row, and the tile decode once per workgroup.
 #include "common.hpp"
 #include "keys.hpp"
+#include "luma.hpp"
 #include "ops.hpp"
 
 namespace srcnn {
@@ -58,16 +59,12 @@ __constant__ Weights c_up = make_weights();
 // The two scale-1 anchors are bit-exact: the plane's interior is
 // srcnn_extract_luma's output and the composition srcnn_swap_luma's.  Under
 // -ffp-contract=fast the compiler chooses which of those kernels' products
-// fuse into an fma, and the choice shows in the last bit; these two helpers
-// spell out the operations extract_luma_kernel and swap_luma_kernel
-// (ops_generic.hip) are built from, with contraction off, so that the
-// context they are inlined into cannot change them
-// (tests/test_upscale_gpu.py pins both against the kernels themselves).
-__device__ __forceinline__ float luma_of(float r, float g, float b) {
-#pragma clang fp contract(off)
-  const float v = fmaf(b, 0.114f, r * 0.299f + g * 0.587f);
-  return v / 255.0f;
-}
+// fuse into an fma, and the choice shows in the last bit; luma_of (luma.hpp,
+// shared with quality.hip) and compose_px spell out the operations
+// extract_luma_kernel and swap_luma_kernel (ops_generic.hip) are built from,
+// with contraction off, so that the context they are inlined into cannot
+// change them (tests/test_upscale_gpu.py pins both against the kernels
+// themselves).
 __device__ __forceinline__ void compose_px(float r, float g, float b, float nl, uint8_t* q) {
 #pragma clang fp contract(off)
   const float Cb = fmaf(b, 0.5f, fmaf(r, -0.1687f, g * -0.3312f));

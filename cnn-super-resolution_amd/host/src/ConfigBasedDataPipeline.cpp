@@ -255,6 +255,41 @@ void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, 
   _context->raw_memory(rgba)->release();
 }
 
+bool ConfigBasedDataPipeline::evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& q_net,
+                                       QualityReport& q_bicubic) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  require(scale >= 1 && scale <= 4, "evaluate: scale must be 1, 2, 3 or 4");
+  require(truth.w > 0 && truth.h > 0, "evaluate: empty image");
+  const uint64_t Wc = uint64_t(truth.w) / scale * scale, Hc = uint64_t(truth.h) / scale * scale;
+  if (Wc < 2 * uint64_t(shave) + 11 || Hc < 2 * uint64_t(shave) + 11) return false;
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "evaluate needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  const size_t ws = srcnn_evaluate_workspace_bytes(&nt, truth.w, truth.h, scale);
+  require(ws > 0, std::string("evaluate: ") + srcnn_last_error());
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, truth.w, truth.h);
+  _context->write_image(rgba, truth, true);
+  MemoryHandle res = _context->allocate(srcnn::MEM_READ_WRITE, 6 * sizeof(double));
+  void* wsp = scratch(ws);
+  if (!_evaluate_kernel)
+    _evaluate_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_evaluate", 0, 0, 0, false,
+                                               "-D SCALE=" + std::to_string(scale));
+  {
+    srcnn::Context::Launch l(*_context, *_evaluate_kernel);
+    check(srcnn_evaluate(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), truth.w, truth.h, scale, shave,
+                         _context->fptr(_flat_params), static_cast<double*>(_context->ptr(res)), wsp, ws,
+                         _context->stream()),
+          "evaluate");
+  }
+  double r[6];
+  _context->read_buffer(res, 0, sizeof(r), r, true);
+  _context->raw_memory(res)->release();
+  _context->raw_memory(rgba)->release();
+  q_net.mse = r[0], q_net.psnr = r[1], q_net.ssim = r[2];
+  q_bicubic.mse = r[3], q_bicubic.psnr = r[4], q_bicubic.ssim = r[5];
+  return true;
+}
+
 // ---------------------------------------------------------------- training
 
 size_t ConfigBasedDataPipeline::make_training_pairs(ImageData& full, unsigned scale, size_t tile,

@@ -122,6 +122,15 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * input_w = input_h = tile. */
   size_t make_training_pairs(ImageData& full, unsigned scale, size_t tile, size_t stride,
                              std::vector<SampleAllocationPool>& out);
+  /** "How many dB over bicubic?": the full-size ground truth in, the quality
+   * of the net's x `scale` result (`net`) and of plain bicubic's (`bicubic`)
+   * out, with `shave` pixels dropped per side: one srcnn_evaluate call on the
+   * pipeline's flat parameters (down by `scale`, super_resolve's resampling
+   * and net, srcnn_quality against the truth's top-left scale*(w/scale) x
+   * scale*(h/scale) pixels).  False, with nothing measured, if what is left
+   * after the crop and the shave is smaller than the 11 x 11 SSIM window. */
+  bool evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& net,
+                QualityReport& bicubic);
   /** L3 output of the last forward / execute_batch chunk */
   MemoryHandle result_buffer() const { return _out_3_gpu_buf; }
   /** the flat [gW1|gB1|gW2|gB2|gW3|gB3] buffer (gpu_nullptr before training
@@ -189,6 +198,7 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
+  Kernel* _evaluate_kernel = nullptr;
   Kernel* _update_all_kernel = nullptr;
   Kernel* _allreduce_kernel = nullptr;
   MemoryHandle _comm_scalar = gpu_nullptr;

@@ -222,6 +222,40 @@ void DataPipeline::downscale(ImageData& img, unsigned scale, ImageData& out) {
   _context->raw_memory(rgba)->release();
 }
 
+QualityReport DataPipeline::quality(ImageData& img, ImageData& ref, unsigned shave) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(img.w > 0 && img.h > 0, "quality: empty image");
+  require(img.w == ref.w && img.h == ref.h,
+          "quality: the images differ in size: " + std::to_string(img.w) + "x" + std::to_string(img.h) +
+              " / " + std::to_string(ref.w) + "x" + std::to_string(ref.h));
+  const size_t ws = srcnn_quality_workspace_bytes(img.w, img.h, shave);
+  require(ws > 0, std::string("quality: ") + srcnn_last_error());
+  MemoryHandle a = _context->create_image(srcnn::MEM_READ_WRITE, img.w, img.h);
+  MemoryHandle b = _context->create_image(srcnn::MEM_READ_WRITE, ref.w, ref.h);
+  _context->write_image(a, img, true);
+  _context->write_image(b, ref, true);
+  MemoryHandle res = _context->allocate(srcnn::MEM_READ_WRITE, 3 * sizeof(double));
+  void* wsp = scratch(ws);
+  if (!_quality_kernel) _quality_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_quality");
+  {
+    srcnn::Context::Launch l(*_context, *_quality_kernel);
+    check(srcnn_quality(_context->ptr(a), SRCNN_PIX_RGBA8, img.w, _context->ptr(b), SRCNN_PIX_RGBA8, ref.w,
+                        img.w, img.h, shave, static_cast<double*>(_context->ptr(res)), wsp, ws,
+                        _context->stream()),
+          "quality");
+  }
+  double r[3];
+  _context->read_buffer(res, 0, sizeof(r), r, true);
+  _context->raw_memory(res)->release();
+  _context->raw_memory(b)->release();
+  _context->raw_memory(a)->release();
+  QualityReport q;
+  q.mse = r[0];
+  q.psnr = r[1];
+  q.ssim = r[2];
+  return q;
+}
+
 Event DataPipeline::gather_tiles(MemoryHandle plane, size_t pw, size_t ph, size_t x0, size_t y0,
                                  size_t stride, size_t nx, size_t ny, size_t tw, size_t th,
                                  bool sub_mean, MemoryHandle& tiles, MemoryHandle* means, Event* ev) {

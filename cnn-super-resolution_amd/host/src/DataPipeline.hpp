@@ -31,6 +31,11 @@ struct LayerAllocationPool {
   MemoryHandle previous_batch_delta_b = gpu_nullptr;
 };
 
+/** srcnn_quality's three results (psnr is +inf for identical images). */
+struct QualityReport {
+  double mse = 0, psnr = 0, ssim = 0;
+};
+
 class DataPipeline {
  public:
   static int LOAD_KERNEL_LUMA;
@@ -74,6 +79,11 @@ class DataPipeline {
    * downscaled by `scale` (1..4) on the device into `out`, RGBA of
    * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
   void downscale(ImageData& img, unsigned scale, ImageData& out);
+
+  /** Extension: PSNR and SSIM of `img` against `ref` (equal sizes, any of 1,
+   * 3 or 4 channels each), measured on the device on the full-range luma
+   * with `shave` pixels dropped per side (srcnn_quality).  Blocking. */
+  QualityReport quality(ImageData& img, ImageData& ref, unsigned shave);
 
   /** Extension: cut nx x ny tiles of tw x th floats, tile (ix, iy) from
    * (x0 + ix*stride, y0 + iy*stride), out of the plane_w x plane_h float plane
@@ -156,6 +166,7 @@ class DataPipeline {
   Kernel* _upscale_compose_kernel = nullptr;
   Kernel* _downscale_kernel = nullptr;
   Kernel* _gather_tiles_kernel = nullptr;
+  Kernel* _quality_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;
   Kernel* _sum_squared_kernel = nullptr;

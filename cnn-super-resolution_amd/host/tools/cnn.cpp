@@ -1,10 +1,10 @@
 // cnn -- the command line of the reference (src/Main_cl.cpp) on the MI355X
 // pipeline:
 //
-//   cnn [-h] [train | upscale | downscale] [dry] [profile] -c CONFIG -i IN [-o OUT]
-//       [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]
-//       [--validation-percent P] [--mini-batches M] [--save-momentum]
-//       [--from-images] [--tile N] [--stride N]
+//   cnn [-h] [train | upscale | downscale | quality | evaluate] [dry] [profile]
+//       -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]
+//       [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]
+//       [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -18,6 +18,16 @@
 //           size (RGB), resampled on the device by the inverse of the upscale
 //           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
 //           for `cnn upscale`.  Needs no CONFIG.
+// quality:  (extension) IN and --ref REF are two image files of equal size; prints
+//           the PSNR, SSIM and MSE of IN against REF, measured on the device
+//           on the full-range luma (srcnn_quality), --shave pixels dropped per
+//           side (default 0).  Needs no CONFIG and no OUT.
+// evaluate: (extension) IN is a full-size image or a directory of them; each
+//           is downscaled by S, upscaled again by the net and by plain bicubic
+//           on the device and both results are measured against the image
+//           (srcnn_evaluate): one line per image with the net's and bicubic's
+//           PSNR and SSIM and the gain in dB, then the means.  --shave defaults
+//           to S (the literature's rule); -o writes the numbers as JSON.
 // train:    IN is a directory of <name>_large.<ext> / <name>_small.<ext> pairs
 //           (ground truth / degraded input, tools/make_samples.py makes
 //           them), OUT the parameters.json written at the end.
@@ -45,6 +55,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <mutex>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -67,13 +78,16 @@ using namespace cnn_sr;
 namespace {
 
 struct Args {
-  bool train = false, upscale = false, downscale = false, dry = false, profile = false, help = false, version = false;
+  bool train = false, upscale = false, downscale = false, quality = false, evaluate = false, dry = false, profile = false, help = false, version = false;
   unsigned scale = 2;      // upscale, downscale, train --from-images: --scale
   bool scale_set = false;
   bool from_images = false;  // train --from-images: cut the pairs on the device
   size_t tile = 33, stride = 14;
   bool tile_set = false, stride_set = false;
   std::string config, in, out;
+  std::string ref;       // quality: --ref
+  unsigned shave = 0;    // quality, evaluate: --shave (evaluate: default --scale)
+  bool shave_set = false;
   size_t epochs = 0;
   uint64_t seed = 0;
   bool seeded = false;
@@ -89,10 +103,10 @@ struct Args {
 
 void usage() {
   std::cout
-      << "usage: cnn [-h] [train | upscale | downscale] [dry] [profile] -c CONFIG -i IN [-o OUT]\n"
-         "           [-e EPOCHS] [--scale S] [--seed N] [--device D] [--devices N]\n"
-         "           [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
-         "           [--from-images] [--tile N] [--stride N]\n\n"
+      << "usage: cnn [-h] [train | upscale | downscale | quality | evaluate] [dry] [profile]\n"
+         "           -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]\n"
+         "           [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
+         "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
@@ -102,6 +116,14 @@ void usage() {
          "  downscale             downscale mode: IN is a full-size image, OUT the image of\n"
          "                        1 / --scale the size (the inverse of the upscale mode's\n"
          "                        bicubic, on the device; -c is not needed)\n"
+         "  quality               quality mode: PSNR, SSIM and MSE of the image IN against\n"
+         "                        --ref REF (equal sizes), measured on the device on the\n"
+         "                        full-range luma; -c and -o are not needed\n"
+         "  evaluate              evaluate mode: IN is a full-size image or a directory of\n"
+         "                        them; each is downscaled by --scale, upscaled again by the\n"
+         "                        net and by plain bicubic, and both are measured against\n"
+         "                        it: PSNR, SSIM and the gain in dB per image and their\n"
+         "                        means; -o writes them as JSON\n"
          "  dry                   do not store the result\n"
          "  profile               print kernel execution times\n"
          "  -c, --config CONFIG   CNN configuration (config.json)\n"
@@ -109,9 +131,12 @@ void usage() {
          "                        training\n"
          "  -o, --out OUT         output path (result image or new parameters file)\n"
          "  -e, --epochs EPOCHS   number of epochs during training\n"
-         "  --scale S             scale factor 1, 2, 3 or 4 (default 2; upscale, downscale\n"
-         "                        and train --from-images only; upscale 1: same size, every\n"
-         "                        pixel through the net)\n"
+         "  --scale S             scale factor 1, 2, 3 or 4 (default 2; upscale, downscale,\n"
+         "                        evaluate and train --from-images only; upscale 1: same\n"
+         "                        size, every pixel through the net)\n"
+         "  --ref REF             quality: the image IN is measured against\n"
+         "  --shave N             quality, evaluate: pixels dropped on every side before\n"
+         "                        measuring (default: 0 for quality, --scale for evaluate)\n"
          "  --from-images         train: IN is a directory of full-size images; the sample\n"
          "                        pairs are cut on the device, the inputs degraded by\n"
          "                        --scale as the upscale mode resamples\n"
@@ -141,6 +166,22 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "train") a.train = true;
     else if (s == "upscale") a.upscale = true;
     else if (s == "downscale") a.downscale = true;
+    else if (s == "quality") a.quality = true;
+    else if (s == "evaluate") a.evaluate = true;
+    else if (s == "--ref") a.ref = value("--ref");
+    else if (s == "--shave") {
+      const std::string v = value("--shave");
+      size_t n = 0, used = 0;
+      try {
+        n = std::stoul(v, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used != v.size() || v.empty() || v[0] == '-' || n > 0x7fffffffu)
+        throw std::runtime_error("--shave must be a non-negative integer");
+      a.shave = unsigned(n);
+      a.shave_set = true;
+    }
     else if (s == "--from-images") a.from_images = true;
     else if (s == "--tile" || s == "--stride") {
       const std::string v = value(s.c_str());
@@ -184,14 +225,21 @@ bool parse(int argc, char** argv, Args& a) {
     else throw std::runtime_error("unknown argument '" + s + "'");
   }
   if (a.help || a.version) return false;
-  if (int(a.upscale) + int(a.train) + int(a.downscale) > 1)
-    throw std::runtime_error("train, upscale and downscale are different modes");
+  if (int(a.upscale) + int(a.train) + int(a.downscale) + int(a.quality) + int(a.evaluate) > 1)
+    throw std::runtime_error("train, upscale, downscale, quality and evaluate are different modes");
   if (a.from_images && !a.train) throw std::runtime_error("--from-images needs the train mode");
   if ((a.tile_set || a.stride_set) && !a.from_images)
     throw std::runtime_error("--tile and --stride need train --from-images");
-  if (a.scale_set && !a.upscale && !a.downscale && !a.from_images)
-    throw std::runtime_error("--scale needs the upscale mode, the downscale mode or train --from-images");
-  if (a.downscale) {
+  if (a.scale_set && !a.upscale && !a.downscale && !a.evaluate && !a.from_images)
+    throw std::runtime_error(
+        "--scale needs the upscale mode, the downscale mode, the evaluate mode or train --from-images");
+  if (!a.ref.empty() && !a.quality) throw std::runtime_error("--ref needs the quality mode");
+  if (a.shave_set && !a.quality && !a.evaluate)
+    throw std::runtime_error("--shave needs the quality mode or the evaluate mode");
+  if (a.evaluate && !a.shave_set) a.shave = a.scale;  // the literature's rule
+  if (a.quality) {
+    if (a.in.empty() || a.ref.empty()) throw std::runtime_error("--in and --ref are required");
+  } else if (a.downscale) {
     if (a.in.empty()) throw std::runtime_error("--in is required");
   } else if (a.config.empty() || a.in.empty()) {
     throw std::runtime_error("--config and --in are required");
@@ -281,6 +329,119 @@ int downscale(DataPipeline& p, const Args& a) {
       for (int c = 0; c < 3; ++c) rgb.data[3 * i + c] = small.data[4 * i + c];
     std::cout << "Saving result image to: '" << a.out << "'" << std::endl;
     srcnn::image::write(a.out.c_str(), rgb);
+  }
+  p.context()->block();
+  return 0;
+}
+
+/** doubles as the reports print them: 17 significant digits, so that a reader
+ * gets the device's value back bit for bit; "inf" for identical images */
+std::string num(double v) {
+  if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+  char buf[40];
+  std::snprintf(buf, sizeof(buf), "%.17g", v);
+  return buf;
+}
+/** the same for the JSON report, which has no infinity: null */
+std::string json_num(double v) { return std::isfinite(v) ? num(v) : "null"; }
+
+/** `cnn quality`: the image against --ref through srcnn_quality */
+int quality(DataPipeline& p, const Args& a) {
+  ImageData img, ref;
+  srcnn::image::load(a.in, img, 4);
+  srcnn::image::load(a.ref, ref, 4);
+  srcnn::require(img.w == ref.w && img.h == ref.h,
+                 "the images differ in size: " + std::to_string(img.w) + "x" + std::to_string(img.h) + " / " +
+                     std::to_string(ref.w) + "x" + std::to_string(ref.h));
+  srcnn::require(uint64_t(img.w) >= 2 * uint64_t(a.shave) + 11 && uint64_t(img.h) >= 2 * uint64_t(a.shave) + 11,
+                 "image " + std::to_string(img.w) + "x" + std::to_string(img.h) + " with " +
+                     std::to_string(a.shave) + " pixels shaved per side is smaller than the 11x11 SSIM window");
+  const QualityReport q = p.quality(img, ref, a.shave);
+  std::cout << "psnr: " << num(q.psnr) << " dB" << std::endl
+            << "ssim: " << num(q.ssim) << std::endl
+            << "mse: " << num(q.mse) << std::endl;
+  p.context()->block();
+  return 0;
+}
+
+/** `cnn evaluate`: IN, or every file of the directory IN that decodes, in name
+ * order, through srcnn_evaluate */
+int evaluate(ConfigBasedDataPipeline& p, const Args& a) {
+  std::vector<std::string> names;  // relative to `base`
+  std::string base;
+  if (DIR* d = opendir(a.in.c_str())) {
+    while (dirent* e = readdir(d)) {
+      std::string f = e->d_name;
+      if (f != "." && f != "..") names.push_back(f);
+    }
+    closedir(d);
+    std::sort(names.begin(), names.end());
+    base = a.in + "/";
+  } else {
+    names.push_back(a.in);
+  }
+  struct Row {
+    std::string name;
+    int w, h;
+    QualityReport net, bic;
+  };
+  std::vector<Row> rows;
+  for (auto& f : names) {
+    ImageData img;
+    try {
+      srcnn::image::load(base + f, img, 4);
+    } catch (const std::exception& e) {
+      if (base.empty()) throw;  // a single file that does not decode is an error
+      std::cout << "'" << f << "' does not decode (" << e.what() << "). Skipping image" << std::endl;
+      continue;
+    }
+    Row r{f, img.w, img.h, {}, {}};
+    if (!p.evaluate(img, a.scale, a.shave, r.net, r.bic)) {
+      std::cout << "'" << f << "' (" << img.w << "x" << img.h << ") is too small for one 11x11 window at scale "
+                << a.scale << " with " << a.shave << " pixels shaved. Skipping image" << std::endl;
+      continue;
+    }
+    std::cout << "'" << f << "' (" << img.w << "x" << img.h << "): net psnr " << num(r.net.psnr) << " dB ssim "
+              << num(r.net.ssim) << " | bicubic psnr " << num(r.bic.psnr) << " dB ssim " << num(r.bic.ssim)
+              << " | gain " << num(r.net.psnr - r.bic.psnr) << " dB" << std::endl;
+    rows.push_back(r);
+  }
+  if (rows.empty()) throw std::runtime_error("no image to evaluate in '" + a.in + "'");
+  QualityReport mn, mb;
+  for (auto& r : rows) {
+    mn.psnr += r.net.psnr / rows.size(), mn.ssim += r.net.ssim / rows.size();
+    mb.psnr += r.bic.psnr / rows.size(), mb.ssim += r.bic.ssim / rows.size();
+  }
+  std::cout << "mean over " << rows.size() << " images: net psnr " << num(mn.psnr) << " dB ssim " << num(mn.ssim)
+            << " | bicubic psnr " << num(mb.psnr) << " dB ssim " << num(mb.ssim) << " | gain "
+            << num(mn.psnr - mb.psnr) << " dB" << std::endl;
+  if (!a.dry && !a.out.empty()) {
+    std::ofstream out(a.out);
+    if (!out) throw srcnn::IOException("cannot write report '" + a.out + "'");
+    auto esc = [](const std::string& s) {
+      std::string o;
+      for (char c : s) {
+        if (c == '"' || c == '\\') o += '\\';
+        if ((unsigned char)c < 0x20) o += ' ';
+        else o += c;
+      }
+      return o;
+    };
+    auto q = [&](const QualityReport& r, bool with_mse) {
+      return "{\"psnr\": " + json_num(r.psnr) + ", \"ssim\": " + json_num(r.ssim) +
+             (with_mse ? ", \"mse\": " + json_num(r.mse) : std::string()) + "}";
+    };
+    out << "{\n  \"scale\": " << a.scale << ",\n  \"shave\": " << a.shave << ",\n  \"images\": [\n";
+    for (size_t i = 0; i < rows.size(); ++i) {
+      auto& r = rows[i];
+      out << "    {\"name\": \"" << esc(r.name) << "\", \"width\": " << r.w << ", \"height\": " << r.h
+          << ", \"net\": " << q(r.net, true) << ", \"bicubic\": " << q(r.bic, true)
+          << ", \"gain_db\": " << json_num(r.net.psnr - r.bic.psnr) << "}" << (i + 1 < rows.size() ? "," : "")
+          << "\n";
+    }
+    out << "  ],\n  \"mean\": {\"count\": " << rows.size() << ", \"net\": " << q(mn, false)
+        << ", \"bicubic\": " << q(mb, false) << ", \"gain_db\": " << json_num(mn.psnr - mb.psnr) << "}\n}\n";
+    std::cout << "Saving report to: '" << a.out << "'" << std::endl;
   }
   p.context()->block();
   return 0;
@@ -578,7 +739,7 @@ int main(int argc, char** argv) {
     usage();
     return 1;
   }
-  if (!a.dry && a.out.empty()) {
+  if (!a.dry && a.out.empty() && !a.quality && !a.evaluate) {  // (those two print their result)
     std::cout << "Either provide out path or do the dry run" << std::endl;
     return 1;
   }
@@ -596,6 +757,14 @@ int main(int argc, char** argv) {
     std::cout << "Downscale mode, scale: " << a.scale << std::endl
               << "Input image: " << a.in << std::endl
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
+  else if (a.quality)
+    std::cout << "Quality mode, shave: " << a.shave << std::endl
+              << "Input image: " << a.in << std::endl
+              << "Reference image: " << a.ref << std::endl;
+  else if (a.evaluate)
+    std::cout << "Evaluate mode, scale: " << a.scale << ", shave: " << a.shave << std::endl
+              << "Full-size image or directory: " << a.in << std::endl
+              << "Report: " << (a.dry || a.out.empty() ? "-" : a.out) << std::endl;
   else if (a.upscale)
     std::cout << "Upscale mode, scale: " << a.scale << std::endl
               << "Input image: " << a.in << std::endl
@@ -612,6 +781,13 @@ int main(int argc, char** argv) {
       pipeline.init(DataPipeline::LOAD_KERNEL_LUMA);
       return downscale(pipeline, a);
     }
+    if (a.quality) {
+      srcnn::Context context;
+      context.init(a.profile, a.device);
+      DataPipeline pipeline(&context);
+      pipeline.init(DataPipeline::LOAD_KERNEL_LUMA);
+      return quality(pipeline, a);
+    }
     ConfigReader reader;
     Config cfg = reader.read(a.config.c_str());
     std::cout << cfg << std::endl;
@@ -623,9 +799,10 @@ int main(int argc, char** argv) {
       ConfigBasedDataPipeline pipeline(cfg, &context);
       if (a.seeded) pipeline.set_random_seed(a.seed);
       pipeline.init(DataPipeline::LOAD_KERNEL_ALL);
-      rc = a.train     ? train(pipeline, a, a.seeded ? a.seed : std::random_device{}())
-           : a.upscale ? upscale(pipeline, a)
-                       : forward(pipeline, a);
+      rc = a.train      ? train(pipeline, a, a.seeded ? a.seed : std::random_device{}())
+           : a.upscale  ? upscale(pipeline, a)
+           : a.evaluate ? evaluate(pipeline, a)
+                        : forward(pipeline, a);
     }
     return rc;
   } catch (const std::exception& e) {

@@ -89,8 +89,12 @@ SIGNATURES = {
     "srcnn_make_pairs_count": (_S, [_U, _U, _U, _U, _U, ctypes.POINTER(_U), ctypes.POINTER(_U)]),
     "srcnn_make_pairs_workspace_bytes": (_S, [_U, _U, _U]),
     "srcnn_make_pairs": (_I, [_P, _U, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
+    "srcnn_quality_workspace_bytes": (_S, [_U, _U, _U]),
+    "srcnn_quality": (_I, [_P, _I, _U, _P, _I, _U, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
+    "srcnn_evaluate_workspace_bytes": (_S, [_NP, _U, _U, _U]),
+    "srcnn_evaluate": (_I, [_NP, _P, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
     "srcnn_net_param_count": (_S, [_NP]),
     "srcnn_train_workspace_bytes": (_S, [_NP, _U, _U, _U]),
@@ -142,6 +146,8 @@ class SrcnnError(RuntimeError):
 
 OK, ERR_INVALID, ERR_HIP, ERR_WORKSPACE, ERR_ALLOC, ERR_COMM = 0, -1, -2, -3, -4, -5
 COMM_ID_BYTES = 128
+# pixel formats of srcnn_quality (SRCNN_PIX_*)
+PIX_LUMA_F32, PIX_RGB8, PIX_RGBA8 = 1, 3, 4
 
 
 def _call(name, *args):
@@ -360,6 +366,18 @@ def make_pairs(rgba, W, H, scale, tile, stride, X, T, ws, ws_bytes, s=None):
           ws_bytes, s)
 
 
+def quality_workspace_bytes(W, H, shave=0):
+    return _lib.srcnn_quality_workspace_bytes(W, H, shave)
+
+
+def quality(a, fmt_a, pitch_a, b, fmt_b, pitch_b, W, H, shave, result, ws, ws_bytes, s=None):
+    """{mse, psnr, ssim} (3 doubles, device) of the luma of two W x H images,
+    each PIX_RGB8 / PIX_RGBA8 / PIX_LUMA_F32 with its own pitch in pixels,
+    `shave` pixels dropped per side (srcnn_quality)."""
+    _call("srcnn_quality", ptr(a), fmt_a, pitch_a, ptr(b), fmt_b, pitch_b, W, H, shave, ptr(result),
+          ptr(ws), ws_bytes, s)
+
+
 # ---- network level ----
 def net_offsets(net):
     arr = (_S * 6)()
@@ -463,6 +481,19 @@ def upscale(net, rgba, w, h, scale, params, rgb, ws, ws_bytes, s=None):
     padded plane, forward, upscale_compose."""
     _call("srcnn_upscale", ctypes.byref(net), ptr(rgba), w, h, scale, ptr(params), ptr(rgb),
           ptr(ws), ws_bytes, s)
+
+
+def evaluate_workspace_bytes(net, W, H, scale):
+    return _lib.srcnn_evaluate_workspace_bytes(ctypes.byref(net), W, H, scale)
+
+
+def evaluate(net, rgba, W, H, scale, shave, params, result, ws, ws_bytes, s=None):
+    """Full-size ground truth rgba [H][W][4] u8 -> result (6 doubles, device):
+    {mse, psnr, ssim} of the net's x scale result, then of plain bicubic's
+    (srcnn_evaluate): downscale_rgba, upscale, quality, upscale_luma (pad 0),
+    upscale_compose, quality."""
+    _call("srcnn_evaluate", ctypes.byref(net), ptr(rgba), W, H, scale, shave, ptr(params),
+          ptr(result), ptr(ws), ws_bytes, s)
 
 
 def set_path(p):

@@ -266,6 +266,52 @@ SRCNN_API int srcnn_make_pairs(const uint8_t* rgba, uint32_t W, uint32_t H, uint
                                uint32_t tile, uint32_t stride, float* X, float* T, void* ws,
                                size_t ws_bytes, srcnn_stream_t stream);
 
+/* PSNR and SSIM of two images, on the device (an MI355X extension; the
+ * reference has no metric code: DESIGN.md 12.1 is the spec).  a and b are W x H
+ * pixels, each in its own format and with its own row pitch in pixels (pitch
+ * >= W; a sub-window of a larger image is a pointer offset plus the pitch):
+ *   SRCNN_PIX_RGB8      3 bytes per pixel, any byte alignment of the base
+ *                       (what srcnn_upscale writes)
+ *   SRCNN_PIX_RGBA8     4 bytes per pixel, 4-byte aligned (the decoders',
+ *                       srcnn_downscale_rgba's)
+ *   SRCNN_PIX_LUMA_F32  normalised luma (srcnn_extract_luma with normalize,
+ *                       srcnn_forward), 4-byte aligned
+ * Both are measured on the luma at the 0 - 255 scale, Y = 0.299f r + 0.587f g
+ * + 0.114f b with srcnn_extract_luma's operation sequence (Y = 255.0f v for
+ * the float format), not rounded, not clamped: the project's full-range luma,
+ * not Matlab's studio-range rgb2ycbcr.  `shave` pixels are dropped on all four
+ * sides first; Ws = W - 2*shave and Hs = H - 2*shave must be at least 11.
+ *
+ * result (device, 3 doubles) = {mse, psnr, ssim}: mse = the mean over Ws*Hs of
+ * (Ya - Yb)^2, each square formed in fp32 and summed in double; psnr =
+ * 10 log10(255^2 / mse), +inf for mse == 0; ssim = the mean over the
+ * (Ws-10) x (Hs-10) valid placements of the 11 x 11 Gaussian window (sigma
+ * 1.5) of Wang et al.'s SSIM with C1 = (0.01*255)^2, C2 = (0.03*255)^2, fp32
+ * per window on the lumas centred at 128, summed in double.  Identical images
+ * give exactly {0, +inf, 1}.  No atomics: the order of both sums depends on
+ * (Ws, Hs) alone -- not on the pitches, the formats, where the window sits in
+ * a larger buffer or what lies around it -- so that srcnn_quality(shave = k)
+ * is bit-identical to the call on the pointer-offset interior with shave = 0,
+ * and two calls on the same inputs are bit-identical.
+ *
+ * `ws` (srcnn_quality_workspace_bytes: two doubles per workgroup) falls under
+ * the memory contract at srcnn_train_workspace_bytes; the call writes the
+ * three doubles of result and reads a and b inside the shaved window only.
+ * Stream-ordered, two launches, no host synchronisation.
+ *
+ * SRCNN_ERR_INVALID, before any launch: an unknown format; a null buffer;
+ * pitch < W; Ws < 11 or Hs < 11 (2*shave wrapping around included); an RGBA8
+ * or F32 base that is not 4-byte aligned (result and ws, which hold doubles:
+ * 8-byte); or a size beyond the kernels' 32-bit index (pitch*H pixels of
+ * either image must number at most 2^31-1).
+ * SRCNN_ERR_WORKSPACE for a workspace that is too small;
+ * srcnn_quality_workspace_bytes returns 0 for invalid sizes. */
+enum { SRCNN_PIX_LUMA_F32 = 1, SRCNN_PIX_RGB8 = 3, SRCNN_PIX_RGBA8 = 4 };
+SRCNN_API size_t srcnn_quality_workspace_bytes(uint32_t W, uint32_t H, uint32_t shave);
+SRCNN_API int srcnn_quality(const void* a, int fmt_a, uint32_t pitch_a, const void* b, int fmt_b,
+                            uint32_t pitch_b, uint32_t W, uint32_t H, uint32_t shave,
+                            double* result, void* ws, size_t ws_bytes, srcnn_stream_t stream);
+
 /* ---- network level: ConfigBasedDataPipeline (src/ConfigBasedDataPipeline.cpp) ---- */
 typedef struct srcnn_net {
   uint32_t n1, n2, f1, f2, f3; /* Config n1,n2,f1,f2,f3 (src/Config.hpp:27-28) */
@@ -273,7 +319,7 @@ typedef struct srcnn_net {
 
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
  * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale) launch
- * for this net, and the kernels of srcnn_make_pairs.
+ * for this net, and the kernels of srcnn_make_pairs and srcnn_quality.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -302,7 +348,7 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
  *     A3 extent; srcnn_train_activations: the three extents it documents;
  *     rgb: 3*W*H bytes; srcnn_make_pairs: count*tile*tile floats of X and of
- *     T each);
+ *     T each; srcnn_quality / srcnn_evaluate: the 3 / 6 doubles of result);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
@@ -357,6 +403,31 @@ SRCNN_API size_t srcnn_upscale_workspace_bytes(const srcnn_net* net, uint32_t w,
 SRCNN_API int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h,
                             uint32_t scale, const float* params, uint8_t* rgb, void* ws,
                             size_t ws_bytes, srcnn_stream_t stream);
+
+/* "How many dB over bicubic?" in one call: the full-size ground truth rgba
+ * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at
+ * scale s come out: result (device, 6 doubles) = {net mse, psnr, ssim, bicubic
+ * mse, psnr, ssim}.  With w = W/s, h = H/s, Wc = s*w, Hc = s*h it is result for
+ * result bit-identical to
+ *   srcnn_downscale_rgba(rgba -> small [h][w][4])
+ *   srcnn_upscale(net, small -> rgb [Hc][Wc][3])
+ *   srcnn_quality(rgb, RGB8, Wc; rgba, RGBA8, W; Wc, Hc, shave) -> result[0..2]
+ *   srcnn_upscale_luma(small, pad = 0) -> plane [Hc][Wc]
+ *   srcnn_upscale_compose(small, plane -> rgb)
+ *   srcnn_quality(as above)                                     -> result[3..5]
+ * Stream-ordered, no host synchronisation, no allocation.  `ws` holds the
+ * low-resolution image, one rgb buffer, the luma plane, srcnn_upscale's
+ * workspace and srcnn_quality's (each 256-byte aligned) under the memory
+ * contract at srcnn_train_workspace_bytes; the call writes the six doubles of
+ * result.  srcnn_evaluate_workspace_bytes returns 0 for an invalid net, scale
+ * or size.  Errors as srcnn_downscale_rgba, srcnn_upscale and srcnn_quality
+ * (Wc - 2*shave and Hc - 2*shave at least 11), before any launch, plus
+ * SRCNN_ERR_WORKSPACE for a workspace that is too small. */
+SRCNN_API size_t srcnn_evaluate_workspace_bytes(const srcnn_net* net, uint32_t W, uint32_t H,
+                                                uint32_t scale);
+SRCNN_API int srcnn_evaluate(const srcnn_net* net, const uint8_t* rgba, uint32_t W, uint32_t H,
+                             uint32_t scale, uint32_t shave, const float* params, double* result,
+                             void* ws, size_t ws_bytes, srcnn_stream_t stream);
 
 /* ---- profiling: the reference's `profile` mode (src/opencl/Kernel.cpp:108-116,
  * src/opencl/Context.cpp:88-96) without blocking per launch: when enabled,
