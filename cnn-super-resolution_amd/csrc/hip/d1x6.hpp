@@ -30,7 +30,7 @@
 // One wave per SIMD (512 registers: 128 accumulators + operands).
 
 constexpr int kD6W2 = 2 * 2 * 3 * 512;  // delta1's W2 image, bf16: [t][k][part][lane][8]
-constexpr int kD6W3 = 3 * 3 * 512;      // delta2's W3 image (kD3), bf16: [s][part][lane][8]
+constexpr int kD6W3 = 2 * 3 * 512;      // delta2's W3 image (kD3), bf16: [s][part][lane][8]
 constexpr int kD6Sc = 32 * 36;           // per-wave delta2 transpose scratch (floats)
 
 // layer-3 geometry for the kD3 form (delta2 formed here from delta3)
@@ -72,9 +72,10 @@ struct D6Lds {
     gw = gs = gh = d3buf = 0;
     w3i = d3tab = d3img = bytes;
     if (d3) {
-      // slot (py, px) reads delta3 at image row py + 5 - dy, columns px ..
-      // px + 7 (dx = 7 - j); the padded row stride puts a chunk's 32 slots on
-      // 32 banks (as l12x6's X image), unpadded where that does not fit
+      // slot (py, px) reads delta3 at image row py + 5 - dy, column px + 7 -
+      // dx (pairs of columns, d3taps.hpp); the padded row stride puts a
+      // chunk's 32 slots at one fixed offset on 32 banks (as l12x6's X
+      // image), unpadded where that does not fit
       gw = rg.ow + 8;
       gh = rg.oh + 5;
       const int a4 = (4 * rg.a) % 32;
@@ -145,16 +146,20 @@ __device__ __forceinline__ void d6_split(const float (&v)[8], bf16x8 (&o)[3]) { 
 // sample) and each item forms its delta2 rows itself,
 //   delta2T[n][slot] = [A2 > 0] sum_tap W3[tap][n] delta3(slot - off(tap))
 // (layer_deltas.cl:79-123 for layer 2) as one more split-bf16 GEMM: M = n2,
-// N = the 32 slots, K = 3 k-steps of 16 tap slots (k-step s, lane half h,
-// element j: tap dy = 2s + h, dx = 7 - j; zero weights past f3), B = delta3
-// from a per-sample pair image (the 8 values of a slot are consecutive), the
-// relu' mask from A2 rows loaded in place of the delta2 rows.  18 MFMAs per
-// item instead of delta2's HBM round trip (328 MB per 4096-tile step).
+// N = the 32 slots, K = 2 k-steps of 16 tap slots (k-step s, lane half h,
+// element j: pair slot 8s + 4h + (j >> 1) of d3taps.hpp, ceil(f3 / 2) pairs
+// per tap row; zero weights on the unused elements), B = delta3 from a
+// per-sample pair image (the 2 values of a pair are consecutive, each pair
+// dword has its own offset), the relu' mask one dword per slot that l3r wrote
+// after delta3 in the D2 region (M2: bit n = A2[pixel][n] > 0; the A2 rows
+// themselves, 328 MB per 4096-tile step, were read here for that one bit per
+// value).  12 MFMAs per item instead of delta2's HBM round trip (328 MB more).
 template <bool kD3>
 __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __restrict__ X,
                                                               const float* __restrict__ A1T,
                                                               const float* __restrict__ D2,
                                                               const float* __restrict__ A2,
+                                                              const uint32_t* __restrict__ M2,
                                                               const float* __restrict__ W2,
                                                               const float* __restrict__ W3,
                                                               float* __restrict__ slab, Geom g, RunGeom rg,
@@ -258,19 +263,22 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   };
   if constexpr (kD3) {
     // delta2's A operand W3^T: k-step s, part q, lane (n, h), element j <->
-    // W3[tap (2 s + h, 7 - j)][n], zero past f3
-    // (all six loads in flight at once: one per loop trip, each waited
+    // W3[tap of pair slot 8 s + 4 h + (j >> 1), element j & 1][n], zero on
+    // the unused elements (d3taps.hpp)
+    // (all four loads in flight at once: one per loop trip, each waited
     // for, they were 6% of a 512-tile launch)
     __bf16* const w3i = reinterpret_cast<__bf16*>(base + L.w3i);
-    constexpr int kW3It = 3 * 64 * 8 / 256;
+    constexpr int kW3It = 2 * 64 * 8 / 256;
+    static_assert(kW3It * 256 * 3 == kD6W3, "the W3 image: 2 k-steps x 3 parts");
     float w3v[kW3It];
 #pragma unroll
     for (int k = 0; k < kW3It; k++) {
       const int e = threadIdx.x + 256 * k;
       const int j = e & 7, L_ = (e >> 3) & 63, s_ = e >> 9;
-      const int dy = 2 * s_ + (L_ >> 5), dx = 7 - j, n = L_ & 31;
-      const bool in = dy < dg.f3 && dx < dg.f3;
-      w3v[k] = W3[in ? (dy * dg.f3 + dx) * N2 + n : 0];
+      const D3Pair tp = d3_pair_slot(8 * s_ + 4 * (L_ >> 5) + (j >> 1), dg.f3);
+      const int dx = d3_pair_dx(tp, j & 1, dg.f3), n = L_ & 31;
+      const bool in = dx >= 0;
+      w3v[k] = W3[in ? (tp.dy * dg.f3 + dx) * N2 + n : 0];
       if (!in) w3v[k] = 0.0f;
     }
 #pragma unroll
@@ -334,18 +342,37 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     return smp < g.batch ? smp : (int)blockIdx.x;
   };
   // operand registers from HBM: delta2 rows of this lane's slot (n = 8h ..
-  // 8h+7 and 16 + 8h ..; kD3: A2 rows, n = 4h .. 4h+3, 8 + 4h, ...: crow
-  // order), A1^T runs of this lane's channel
+  // 8h+7 and 16 + 8h ..), A1^T runs of this lane's channel.  kD3: instead of
+  // the rows, the slot's layer-2 relu' mask (l3r's M2: bit n = A2[pixel][n] >
+  // 0; 0 for a dummy slot), shifted by 4h so that bit 8 (r >> 2) + (r & 3) is
+  // channel crow(r, h), register r of the delta2 GEMM's result
   f32x4 d2r[4], a1r[2][4];
+  uint32_t d2m = 0, d2raw = 0;
+  int d2pix = 0;
   auto ld_d2 = [&](int j, int c) {
     const int pix = slots[c * 32 + li];
-    const float* src = kD3 ? A2 : D2;
-    // every 16-B load of a dummy slot lies inside the zero row, in both modes
-    static_assert(d6_zero_row_covers(false) && d6_zero_row_covers(true), "dummy-slot loads past g_d6_zero");
-    const float* d2 = pix >= 0 ? src + ((size_t)item_sample(j) * npx + pix) * N2 + d6_row_half(kD3, h)
-                               : g_d6_zero + d6_zero_half(kD3, h);
+    if constexpr (kD3) {
+      // (only the load here; the select and shift wait for it at the use)
+      d2pix = pix;
+      d2raw = M2[(size_t)item_sample(j) * npx + (pix >= 0 ? pix : 0)];
+    } else {
+      // every 16-B load of a dummy slot lies inside the zero row
+      static_assert(d6_zero_row_covers(false), "dummy-slot loads past g_d6_zero");
+      const float* d2 = pix >= 0 ? D2 + ((size_t)item_sample(j) * npx + pix) * N2 + d6_row_half(false, h)
+                                 : g_d6_zero + d6_zero_half(false, h);
 #pragma unroll
-    for (int k = 0; k < 4; k++) d2r[k] = *reinterpret_cast<const f32x4*>(d2 + d6_row_quad(kD3, k));
+      for (int k = 0; k < 4; k++) d2r[k] = *reinterpret_cast<const f32x4*>(d2 + d6_row_quad(false, k));
+    }
+  };
+  // kD3: register r of the delta2 GEMM's result under the mask (a sign-extended
+  // bit field and an AND: the two VALU ops of a compare and select)
+  auto mask_take = [&]() __attribute__((always_inline)) { d2m = (d2pix >= 0 ? d2raw : 0u) >> (4 * h); };
+  auto mask_d2 = [&](int r, float v) __attribute__((always_inline)) {
+    // (the instruction itself: from shifts or the sbfe builtin the compiler
+    // made and + compare + select; r is a constant once the loops are unrolled)
+    int keep;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(keep) : "v"(d2m), "i"(8 * (r >> 2) + (r & 3)));
+    return __builtin_bit_cast(float, __builtin_bit_cast(int, v) & keep);
   };
   auto ld_a1 = [&](int j, int c, int k0 = 0, int k1 = 8) __attribute__((always_inline)) {
     const float* a1 = A1T + ((size_t)item_sample(j) * nch + c) * (64 * 32) + li * 32 + 4 * h;
@@ -377,18 +404,33 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   // parts (B) of k-step s from buffer j % 3, W3 parts (A) -- and the GEMM
   const __bf16* const w3l = reinterpret_cast<const __bf16*>(base + L.w3i) + lane * 8;
   const int* const d3tab_ = reinterpret_cast<const int*>(base + L.d3tab);
+  // the image offsets of this lane half's pair dwords of k-step s (row 5 -
+  // dy, column col of pair slot 8 s + 4 h + e, d3taps.hpp): d3a for pairs e =
+  // 0 .. 2 (one row, columns 2 apart), d3b for pair 3.  They depend on the
+  // lane half alone, so they are formed once.  Unused pairs (zero weights)
+  // read inside the image as well
+  int d3a[2] = {}, d3b[2] = {};
+  if constexpr (kD3) {
+#pragma unroll
+    for (int s_ = 0; s_ < 2; s_++) {
+      const D3Pair ta = d3_pair_slot(8 * s_ + 4 * h, dg.f3), tb = d3_pair_slot(8 * s_ + 4 * h + 3, dg.f3);
+      d3a[s_] = (5 - ta.dy) * L.gs + ta.col;
+      d3b[s_] = (5 - tb.dy) * L.gs + tb.col;
+    }
+  }
   // (t = the item's d3tab entry, read once per item: read here, each k-step's
   // reads waited for it)
   auto d3read = [&](int j, int t, int s_, bf16x8 (&a)[3], bf16x8 (&b)[3]) __attribute__((always_inline)) {
     const int buf = j - 3 * (j / 3);
-    const int o = L.d3img / 4 + buf * L.d3buf + t + (5 - 2 * s_ - h) * L.gs;
+    const int o = L.d3img / 4 + buf * L.d3buf + t;
+    const int oa = o + d3a[s_], ob = o + d3b[s_];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       u32x4 d;
-      d[0] = u32[o + L.gw * q];
-      d[1] = u32[o + L.gw * q + 2];
-      d[2] = u32[o + L.gw * q + 4];
-      d[3] = u32[o + L.gw * q + 6];
+      d[0] = u32[oa + L.gw * q];
+      d[1] = u32[oa + L.gw * q + 2];
+      d[2] = u32[oa + L.gw * q + 4];
+      d[3] = u32[ob + L.gw * q];
       b[q] = __builtin_bit_cast(bf16x8, d);
       a[q] = *reinterpret_cast<const bf16x8*>(w3l + (s_ * 3 + q) * 512);
     }
@@ -425,18 +467,17 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   };
 
   // kD3: the delta2 GEMM of an item (the operands of k-step 0 read ahead
-  // into ga / gb), masked by its A2 rows in d2r
+  // into ga / gb), masked by its relu' bits in d2m
   auto d2gemm = [&](int j, int t, bf16x8 (&ga)[3], bf16x8 (&gb)[3]) __attribute__((always_inline)) {
     f32x16 acc[2] = {zero16(), zero16()};
-    bf16x8 a1_[3], b1_[3], a2_[3], b2_[3];
+    bf16x8 a1_[3], b1_[3];
     d3read(j, t, 1, a1_, b1_);
     mma_x6_2(ga, gb, acc[0], a1_, b1_, acc[1]);
-    d3read(j, t, 2, a2_, b2_);
-    acc[0] = mma_x6(a2_, b2_, acc[0]);
+    mask_take();
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const float v = acc[0][r] + acc[1][r];
-      d2v[r] = d2r[r >> 2][r & 3] > 0.0f ? v : 0.0f;
+      d2v[r] = mask_d2(r, v);
     }
   };
 
@@ -562,7 +603,7 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
         __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);  // VALU
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-        if (kD3 && i >= 1 && i < 5) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
+        if (kD3 && i == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (the mask dword)
       }
 
       // ---------------- phase B ----------------
@@ -625,30 +666,32 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       xread(0, 0, bx[0]);
       f32x16 gacc[2];  // kD3: the next item's delta2 GEMM, two chains
       if constexpr (kD3) {
-        // the next item's delta2 GEMM (18 MFMAs) as three fenced groups of 6,
-        // each reading the next k-step's operands and carrying half of the
-        // m = 1 delta1 split; its sum and mask go under gW1's first step
+        // the next item's delta2 GEMM (12 MFMAs) as two fenced groups of 6,
+        // one per k-step and accumulator chain: the first reads the second
+        // k-step's operands, each carries half of the m = 1 delta1 split and
+        // half of the next item's A1 loads; the sum and mask go under gW1's
+        // first step
         gacc[0] = zero16();
         gacc[1] = zero16();
 #pragma unroll
-        for (int s_ = 0; s_ < 3; s_++) {
+        for (int s_ = 0; s_ < 2; s_++) {
           bf16x8 na[3], nb[3];
-          if (s_ < 2) d3read(nj, d3t, s_ + 1, na, nb);
-          ld_a1(nj, nc, 3 * s_, s_ < 2 ? 3 * s_ + 3 : 8);  // (a1r consumed: phase A's split, B's mask)
-          gacc[s_ & 1] = mma_x6(ga, gb, gacc[s_ & 1]);
-          if (s_ < 2) split_d1(1, s_);
+          if (s_ < 1) d3read(nj, d3t, s_ + 1, na, nb);
+          ld_a1(nj, nc, 4 * s_, 4 * s_ + 4);  // (a1r consumed: phase A's split, B's mask)
+          gacc[s_] = mma_x6(ga, gb, gacc[s_]);
+          split_d1(1, s_);
           // (the reads first: placed one per MFMA, the last ones trailed the
           // group and the next group's first MFMA waited for all of them)
-          if (s_ < 2) __builtin_amdgcn_sched_group_barrier(0x100, 9, 0);
+          if (s_ < 1) __builtin_amdgcn_sched_group_barrier(0x100, 9, 0);
 #pragma unroll
           for (int i = 0; i < 6; i++) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (i < 3) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            if (i < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
-          if (s_ < 2) {
+          if (s_ < 1) {
 #pragma unroll
             for (int q = 0; q < 3; q++) {
               ga[q] = na[q];
@@ -669,10 +712,11 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
           // step 0: the delta2 sum, relu' mask and rows into the transpose
           // scratch, 1: the transposed reads and da, 2: da, 3-4: db (+ gbs)
           if (st == 0) {
+            mask_take();
 #pragma unroll
             for (int r = 0; r < 16; r++) {
               const float v = gacc[0][r] + gacc[1][r];
-              d2v[r] = d2r[r >> 2][r & 3] > 0.0f ? v : 0.0f;
+              d2v[r] = mask_d2(r, v);
             }
             stage_d2();
           }

@@ -106,12 +106,14 @@ __device__ __forceinline__ void st_d2(float* p, f32x4 v) {
 // kD3Out (the split-bf16 step): no delta2 here -- the kernel writes the
 // last delta (delta3, w3 x h3 per sample) to D2 instead and d1x6 forms delta2
 // from it (d1x6.hpp), so the 328 MB of delta2 per 4096-tile step never make
-// an HBM round trip and this kernel keeps Q, the window sums and gW3.
+// an HBM round trip and this kernel keeps Q, the window sums and gW3.  It
+// also writes M2, layer 2's relu' mask as one dword per A2 pixel (bit n =
+// A2[pixel][n] > 0), so d1x6 need not read A2 for it.
 template <int F3, bool kD3Out>
 __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wave blocks per CU (128 VGPRs)
     const float* __restrict__ A2, const float* __restrict__ T, const float* __restrict__ W3,
     const float* __restrict__ B3, float* __restrict__ D2, float* __restrict__ slab3,
-    float* __restrict__ sq_slab, float* __restrict__ A3out, L3Geom g) {
+    float* __restrict__ sq_slab, float* __restrict__ A3out, uint32_t* __restrict__ M2, L3Geom g) {
   constexpr int N2 = 32;
   constexpr int K3 = F3 * F3;
   constexpr int TT = (K3 + 15) / 16;  // 16-wide tap tiles
@@ -484,6 +486,45 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
             const f32x4 b_ = *reinterpret_cast<const f32x4*>(scw + g3s + 4 * q);
 #pragma unroll
             for (int i = 0; i < 4; i++) vb[4 * q + i] = b_[i];
+          }
+          // layer 2's relu' mask for d1x6 (M2: one dword per A2 pixel, bit n
+          // = A2[pixel][n] > 0): vb[q] is channel li32 of pixel u0 + 8 h32 + q,
+          // so the wave mask of vb[q] > 0 IS the dwords of pixels u0 + q (low
+          // half) and u0 + 8 + q (high half); lane l < 16 takes pixel u0 + l's
+          // and the unit leaves as one 64-B row (substitute pixels, past the
+          // sample, are not written)
+          {
+            uint32_t m_ = 0;
+            // (the wave masks are uniform, SGPR pairs: of mask q one half goes
+            // into lane q, one into lane 8 + q.  All eight are inputs of ONE
+            // statement that opens with the wait states: the compiler adds
+            // none for inline assembly, and a v_writelane straight after the
+            // v_cmp that wrote its source read the PREVIOUS mask -- every low
+            // half came out one pixel late.  One statement per mask, each with
+            // its own wait, cost l3r 6%: 0.0947 -> 0.1006 ms)
+            uint64_t w_[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) w_[q] = __builtin_amdgcn_ballot_w64(vb[q] > 0.0f);
+#define SRCNN_L3R_LO(Q) "s"((uint32_t)w_[Q])
+#define SRCNN_L3R_HI(Q) "s"((uint32_t)(w_[Q] >> 32))
+            asm volatile(
+                "s_nop 3\n\t"
+                "v_writelane_b32 %0, %1, 0\n\tv_writelane_b32 %0, %2, 1\n\t"
+                "v_writelane_b32 %0, %3, 2\n\tv_writelane_b32 %0, %4, 3\n\t"
+                "v_writelane_b32 %0, %5, 4\n\tv_writelane_b32 %0, %6, 5\n\t"
+                "v_writelane_b32 %0, %7, 6\n\tv_writelane_b32 %0, %8, 7\n\t"
+                "v_writelane_b32 %0, %9, 8\n\tv_writelane_b32 %0, %10, 9\n\t"
+                "v_writelane_b32 %0, %11, 10\n\tv_writelane_b32 %0, %12, 11\n\t"
+                "v_writelane_b32 %0, %13, 12\n\tv_writelane_b32 %0, %14, 13\n\t"
+                "v_writelane_b32 %0, %15, 14\n\tv_writelane_b32 %0, %16, 15"
+                : "+v"(m_)
+                : SRCNN_L3R_LO(0), SRCNN_L3R_LO(1), SRCNN_L3R_LO(2), SRCNN_L3R_LO(3), SRCNN_L3R_LO(4),
+                  SRCNN_L3R_LO(5), SRCNN_L3R_LO(6), SRCNN_L3R_LO(7), SRCNN_L3R_HI(0), SRCNN_L3R_HI(1),
+                  SRCNN_L3R_HI(2), SRCNN_L3R_HI(3), SRCNN_L3R_HI(4), SRCNN_L3R_HI(5), SRCNN_L3R_HI(6),
+                  SRCNN_L3R_HI(7));
+#undef SRCNN_L3R_LO
+#undef SRCNN_L3R_HI
+            if (lane < 16 && u0 + lane < npx2) M2[(size_t)smp * npx2 + u0 + lane] = m_;
           }
           mfma::bf16x8 pa[3], pb[3];
 #pragma unroll

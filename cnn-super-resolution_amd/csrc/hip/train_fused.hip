@@ -350,6 +350,7 @@ __global__ __launch_bounds__(256, 2) void l12_fwd_kernel(
 }
 
 #include "runs.hpp"
+#include "d3taps.hpp"
 #include "l12x6.hpp"
 #include "d1x6.hpp"
 #include "l3_delta.hpp"
@@ -895,15 +896,15 @@ static int grid_for_batch(uint32_t batch, int cap) { return (int)std::min<uint32
 
 template <int F3, bool kD3Out>
 static int launch_l3r(const float* A2, const float* T, const float* W3, const float* B3, float* D2,
-                      float* slab3, float* sqs, float* A3, const L3Geom& lg, int grid, size_t lds,
-                      hipStream_t s) {
+                      float* slab3, float* sqs, float* A3, uint32_t* M2, const L3Geom& lg, int grid,
+                      size_t lds, hipStream_t s) {
   // 70 KB exceeds the 64 KiB default dynamic LDS (set per launch: see launch_l3)
   hipError_t e = hipFuncSetAttribute((const void*)l3r_delta_kernel<F3, kD3Out>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   if (e != hipSuccess)
     return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(l3r_delta): %s", hipGetErrorString(e));
   hipLaunchKernelGGL((l3r_delta_kernel<F3, kD3Out>), dim3(grid), dim3(kL3RThreads), lds, s, A2, T, W3, B3,
-                     D2, slab3, sqs, A3, lg);
+                     D2, slab3, sqs, A3, M2, lg);
   SRCNN_LAUNCH_TRY();
   return SRCNN_OK;
 }
@@ -936,20 +937,21 @@ static int launch_l12x6(const float* X, const float* W1, const float* B1, const 
   return SRCNN_OK;
 }
 
-// kD3: D2 holds delta3 (l3r_delta_kernel<F3, true>) and d1x6 forms delta2
+// kD3: D2 holds delta3 and M2 layer 2's relu' mask (l3r_delta_kernel<F3,
+// true>) and d1x6 forms delta2; A2 is not read then
 static int launch_d1x6(bool kD3, const float* X, const float* A1, const float* D2, const float* A2,
-                       const float* W2, const float* W3, float* slab, const Geom& g, const RunGeom& rg,
-                       const D3Geom& dg, int grid, hipStream_t s) {
+                       const uint32_t* M2, const float* W2, const float* W3, float* slab, const Geom& g,
+                       const RunGeom& rg, const D3Geom& dg, int grid, hipStream_t s) {
   const void* k = kD3 ? (const void*)d1x6_grad12_kernel<true> : (const void*)d1x6_grad12_kernel<false>;
   hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(d1x6_grad12): %s", hipGetErrorString(e));
   const size_t lds = D6Lds(g.W, g.H, rg, kD3).bytes;
   if (kD3)
-    hipLaunchKernelGGL(d1x6_grad12_kernel<true>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, W2, W3, slab, g, rg,
-                       dg);
-  else
-    hipLaunchKernelGGL(d1x6_grad12_kernel<false>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, W2, W3, slab, g,
+    hipLaunchKernelGGL(d1x6_grad12_kernel<true>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, M2, W2, W3, slab, g,
                        rg, dg);
+  else
+    hipLaunchKernelGGL(d1x6_grad12_kernel<false>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, M2, W2, W3, slab,
+                       g, rg, dg);
   SRCNN_LAUNCH_TRY();
   return SRCNN_OK;
 }
@@ -1066,12 +1068,23 @@ static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t 
   if (lz && !l3_fused)
     SRCNN_HIP_TRY(hipMemsetAsync(grads + NetT::P12, 0, NetT::P3 * sizeof(float), s));
   L3Geom lg{(int)w, (int)h, ow, oh, w3, h3, (int)batch};
+  // delta3 mode: the D2 region (sized for delta2: ow * oh * N2 floats per
+  // sample) holds delta3 (w3 * h3 floats per sample) and after it, 256-B
+  // aligned, layer 2's relu' mask (one dword per A2 pixel), written by l3r
+  // and read by d1x6
+  uint32_t* M2 = nullptr;
+  if (d3mode) {
+    const size_t moff = ((size_t)batch * w3 * h3 + 63) & ~(size_t)63;
+    if (moff + (size_t)batch * ow * oh > (size_t)batch * ow * oh * N2)
+      return fail(SRCNN_ERR_INVALID, "fused step: delta3 and the relu' mask exceed the delta2 region");
+    M2 = reinterpret_cast<uint32_t*>(D2) + moff;
+  }
   if (l3_fused) {
     SRCNN_PROFILE("l3_delta_fused", s);
     kernels_note(!l3r ? "l3_delta" : d3mode ? "l3r_d3" : "l3r_delta");
     int rc = !l3r    ? launch_l3<N2, F3>(A2, T, W3, B3, D2, slab3, sqs, A3, lg, g3, lds3, s)
-             : d3mode ? launch_l3r<F3, true>(A2, T, W3, B3, D2, slab3, sqs, A3, lg, g3, lds3, s)
-                      : launch_l3r<F3, false>(A2, T, W3, B3, D2, slab3, sqs, A3, lg, g3, lds3, s);
+             : d3mode ? launch_l3r<F3, true>(A2, T, W3, B3, D2, slab3, sqs, A3, M2, lg, g3, lds3, s)
+                      : launch_l3r<F3, false>(A2, T, W3, B3, D2, slab3, sqs, A3, nullptr, lg, g3, lds3, s);
     if (rc) return rc;
   } else {
     // ConfigBasedDataPipeline.cpp:200-323 for layer 3 on the op-level kernels
@@ -1094,7 +1107,7 @@ static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t 
     kernels_note(x6 ? (d3mode ? "d1x6_d3" : "d1x6_grad12") : kD1c ? "d1c_grad12" : "d1_grad12");
     if (x6) {
       const D3Geom dg{w3, h3, F3};
-      if (int rc = launch_d1x6(d3mode, X, A1, D2, A2, W2, W3, slab12, g, rg, dg, gd6, s)) return rc;
+      if (int rc = launch_d1x6(d3mode, X, A1, D2, A2, M2, W2, W3, slab12, g, rg, dg, gd6, s)) return rc;
     } else if (kD1c)
       hipLaunchKernelGGL((d1c_grad12_kernel<(F1 == 9 ? F1 : 9)>), dim3(gd), dim3(256 * kD1cTeams), d1c_lds_bytes(w, h),
                          s, X, A1, D2, W2, slab12, g, d1c_xs_floats(h), d1c_parts);
