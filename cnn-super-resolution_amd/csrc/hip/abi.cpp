@@ -189,6 +189,16 @@ size_t grad_ws_bytes(uint32_t n_prev, uint32_t n_cur, uint32_t f, uint32_t ow, u
   return b;
 }
 
+// what the family that train_impl will dispatch this shape to needs, under
+// the current path and arithmetic: the fused step, else the wide one, else
+// (the op-level kernels) no slab and A1 in HWC
+srcnn::StepNeed step_need(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch) {
+  srcnn::StepNeed n{0, srcnn::fused::kA1Hwc};
+  if (fast_enabled() && !srcnn::fused::train_plan(net, w, h, batch, &n))
+    srcnn::wide::train_plan(net, w, h, batch, &n);
+  return n;
+}
+
 }  // namespace
 
 extern "C" {
@@ -491,29 +501,14 @@ size_t srcnn_train_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
                        grad_ws_bytes(net->n1, net->n2, net->f2, d.w2, d.h2, batch),
                        grad_ws_bytes(net->n2, 1, net->f3, d.w3, d.h3, batch),
                        srcnn_reduce_workspace_bytes(d.s3 * batch)});
-  size_t fused_need = 0;
-  if (fast_enabled() &&
-      srcnn::fused::train_fwd_bwd(net, nullptr, nullptr, w, h, batch, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                                  true, &fused_need) == 1)
-    g = std::max(g, fused_need);
-  size_t wide_need = 0;
-  if (fast_enabled() &&
-      srcnn::wide::train_fwd_bwd(net, nullptr, nullptr, w, h, batch, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                                 true, &wide_need) == 1)
-    g = std::max(g, wide_need);
-  return b + align_up(g);
+  return b + align_up(std::max(g, step_need(net, w, h, batch).slab_bytes));
 }
 
 // regions of the training workspace (srcnn_train_workspace_bytes): A1 (whole
 // 32-pixel chunks per sample) | D1 | A2 | D2 | A3 | D3 | gradient scratch
-struct TrainWs {
-  float *A1, *D1, *A2, *D2, *A3, *D3;
-  void* gws;
-};
-static TrainWs train_ws(const NetDims& d, uint32_t batch, void* ws) {
-  TrainWs L;
+// (L.slab), as the buffers of a step; the caller's tensors are left null
+static srcnn::StepBuffers train_ws(const NetDims& d, uint32_t batch, void* ws, size_t ws_bytes) {
+  srcnn::StepBuffers L{};
   char* p = static_cast<char*>(ws);
   auto take = [&](size_t floats) {
     float* r = reinterpret_cast<float*>(p);
@@ -526,7 +521,8 @@ static TrainWs train_ws(const NetDims& d, uint32_t batch, void* ws) {
   L.D2 = take(d.s2);
   L.A3 = take(d.s3);
   L.D3 = take(d.s3);
-  L.gws = p;
+  L.slab = reinterpret_cast<float*>(p);
+  L.slab_bytes = ws_bytes - (size_t)(p - static_cast<char*>(ws));
   return L;
 }
 
@@ -545,17 +541,16 @@ static int train_impl(const srcnn_net* net, const float* X, const float* T, uint
   const size_t need = srcnn_train_workspace_bytes(net, w, h, batch);
   if (ws_bytes < need)
     return fail(SRCNN_ERR_WORKSPACE, "train_fwd_bwd: workspace %zu B < %zu B", ws_bytes, need);
-  size_t off[6];
-  srcnn_net_offsets(net, off);
-  const TrainWs L = train_ws(d, batch, ws);
-  float *A1 = L.A1, *D1 = L.D1, *A2 = L.A2, *D2 = L.D2, *A3 = L.A3, *D3 = L.D3;
-  void* gws = L.gws;
-  const size_t gws_bytes = ws_bytes - (size_t)(static_cast<char*>(gws) - static_cast<char*>(ws));
+  srcnn::StepBuffers L = train_ws(d, batch, ws, ws_bytes);
+  L.X = X;
+  L.T = T;
+  L.params = params;
+  L.grads = grads;
+  L.sq_err = sq_err;
+  hipStream_t s = as_stream(stream);
   int rc;
   if (fast_enabled()) {
-    rc = srcnn::fused::train_fwd_bwd(net, X, T, w, h, batch, params, grads, sq_err, A1, A2, D2, A3,
-                                     D3, static_cast<float*>(gws), gws_bytes,
-                                     srcnn::as_stream(stream), false, nullptr, up, lz);
+    rc = srcnn::fused::train_fwd_bwd(net, w, h, batch, L, s, up, lz);
     if (rc == 2 && updated) *updated = true;
     if (rc != 0) return rc < 0 ? rc : tag("fused", SRCNN_OK);
   }
@@ -563,27 +558,21 @@ static int train_impl(const srcnn_net* net, const float* X, const float* T, uint
     // srcnn_train_fwd_bwd_lazy off the fused path: the pending update out of
     // place and the gradients zeroed in one launch, then the accumulating step
     if (lz->batch > 0.0f) {
-      if ((rc = srcnn::lazy_update(*lz, srcnn::as_stream(stream)))) return rc;
-      params = lz->Po;
-    } else if ((rc = srcnn::fill(grads, 0.0f, off[5] + 1, srcnn::as_stream(stream)))) {
+      if ((rc = srcnn::lazy_update(*lz, s))) return rc;
+      L.params = lz->Po;
+    } else if ((rc = srcnn::fill(grads, 0.0f, srcnn_net_param_count(net), s))) {
       return rc;
     }
   }
-  const float *W1 = params + off[0], *B1 = params + off[1], *W2 = params + off[2],
-              *B2 = params + off[3], *W3 = params + off[4], *B3 = params + off[5];
-  float *gW1 = grads + off[0], *gB1 = grads + off[1], *gW2 = grads + off[2],
-        *gB2 = grads + off[3], *gW3 = grads + off[4], *gB3 = grads + off[5];
+  // the wide step and the op-level kernels write A1 in HWC
+  srcnn::fused::note_a1_layout(L.A1, srcnn::fused::kA1Hwc);
   if (fast_enabled()) {
-    rc = srcnn::wide::train_fwd_bwd(net, X, T, w, h, batch, params, grads, sq_err, A1, D1, A2, D2,
-                                    A3, static_cast<float*>(gws), gws_bytes,
-                                    srcnn::as_stream(stream), false, nullptr, up);
+    rc = srcnn::wide::train_fwd_bwd(net, w, h, batch, L, s, up);
     if (rc == 2 && updated) *updated = true;
-    if (rc != 0) {
-      srcnn::fused::note_a1_layout(A1, srcnn::fused::kA1Hwc);
-      return rc < 0 ? rc : tag("wide", SRCNN_OK);
-    }
+    if (rc != 0) return rc < 0 ? rc : tag("wide", SRCNN_OK);
   }
-  srcnn::fused::note_a1_layout(A1, srcnn::fused::kA1Hwc);
+  const auto P = srcnn::split_params(L.params, net);
+  const auto G = srcnn::split_params(grads, net);
   // the op-level launchers (srcnn_last_kernels: one entry per reference
   // launcher, with the kernel family that served it)
   auto op = [](const char* name, int rc) {
@@ -596,33 +585,32 @@ static int train_impl(const srcnn_net* net, const float* X, const float* T, uint
   };
   OpSequence seq;
   // forward: ConfigBasedDataPipeline.cpp:200-241
-  if ((rc = op("conv_fwd_l1", srcnn_conv_fwd(X, A1, W1, B1, w, h, 1, net->n1, net->f1, 1, batch, stream))))
+  if ((rc = op("conv_fwd_l1", srcnn_conv_fwd(X, L.A1, P.W1, P.B1, w, h, 1, net->n1, net->f1, 1, batch, stream))))
     return rc;
   if ((rc = op("conv_fwd_l2",
-               srcnn_conv_fwd(A1, A2, W2, B2, d.w1, d.h1, net->n1, net->n2, net->f2, 1, batch, stream))))
+               srcnn_conv_fwd(L.A1, L.A2, P.W2, P.B2, d.w1, d.h1, net->n1, net->n2, net->f2, 1, batch, stream))))
     return rc;
-  if ((rc = op("conv_fwd_l3", srcnn_conv_fwd(A2, A3, W3, B3, d.w2, d.h2, net->n2, 1, net->f3, 0, batch, stream))))
+  if ((rc = op("conv_fwd_l3", srcnn_conv_fwd(L.A2, L.A3, P.W3, P.B3, d.w2, d.h2, net->n2, 1, net->f3, 0, batch, stream))))
     return rc;
   if (sq_err &&
-      (rc = srcnn::reduce(2, A3, T, d.s3 * batch, w, h, d.w3, d.h3, sq_err, 1, gws, gws_bytes,
-                          srcnn::as_stream(stream))))
+      (rc = srcnn::reduce(2, L.A3, T, d.s3 * batch, w, h, d.w3, d.h3, sq_err, 1, L.slab, L.slab_bytes, s)))
     return rc;
   // backward: ConfigBasedDataPipeline.cpp:243-323
-  if ((rc = srcnn_last_delta(T, A3, D3, w, h, d.w3, d.h3, batch, stream))) return rc;
+  if ((rc = srcnn_last_delta(T, L.A3, L.D3, w, h, d.w3, d.h3, batch, stream))) return rc;
   if ((rc = op("conv_delta_l2",
-               srcnn_conv_delta(D3, A2, D2, W3, net->f3, net->n2, 1, d.w2, d.h2, batch, stream))))
+               srcnn_conv_delta(L.D3, L.A2, L.D2, P.W3, net->f3, net->n2, 1, d.w2, d.h2, batch, stream))))
     return rc;
   if ((rc = op("conv_delta_l1",
-               srcnn_conv_delta(D2, A1, D1, W2, net->f2, net->n1, net->n2, d.w1, d.h1, batch, stream))))
+               srcnn_conv_delta(L.D2, L.A1, L.D1, P.W2, net->f2, net->n1, net->n2, d.w1, d.h1, batch, stream))))
     return rc;
-  if ((rc = op("conv_grad_l3", srcnn_conv_grad_acc(A2, D3, gW3, gB3, net->n2, 1, net->f3, d.w3, d.h3, batch,
-                                                   gws, gws_bytes, stream))))
+  if ((rc = op("conv_grad_l3", srcnn_conv_grad_acc(L.A2, L.D3, G.W3, G.B3, net->n2, 1, net->f3, d.w3, d.h3, batch,
+                                                   L.slab, L.slab_bytes, stream))))
     return rc;
-  if ((rc = op("conv_grad_l2", srcnn_conv_grad_acc(A1, D2, gW2, gB2, net->n1, net->n2, net->f2, d.w2, d.h2,
-                                                   batch, gws, gws_bytes, stream))))
+  if ((rc = op("conv_grad_l2", srcnn_conv_grad_acc(L.A1, L.D2, G.W2, G.B2, net->n1, net->n2, net->f2, d.w2, d.h2,
+                                                   batch, L.slab, L.slab_bytes, stream))))
     return rc;
-  return seq.done(op("conv_grad_l1", srcnn_conv_grad_acc(X, D1, gW1, gB1, 1, net->n1, net->f1, d.w1, d.h1,
-                                                         batch, gws, gws_bytes, stream)));
+  return seq.done(op("conv_grad_l1", srcnn_conv_grad_acc(X, L.D1, G.W1, G.B1, 1, net->n1, net->f1, d.w1, d.h1,
+                                                         batch, L.slab, L.slab_bytes, stream)));
 }
 
 int srcnn_train_fwd_bwd(const srcnn_net* net, const float* X, const float* T, uint32_t w,
@@ -714,22 +702,14 @@ int srcnn_train_activations(const srcnn_net* net, uint32_t w, uint32_t h, uint32
   const size_t need = srcnn_train_workspace_bytes(net, w, h, batch);
   if (ws_bytes < need)
     return fail(SRCNN_ERR_WORKSPACE, "train_activations: workspace %zu B < %zu B", ws_bytes, need);
-  const TrainWs L = train_ws(d, batch, const_cast<void*>(ws));
+  const srcnn::StepBuffers L = train_ws(d, batch, const_cast<void*>(ws), ws_bytes);
   hipStream_t s = as_stream(stream);
-  // the fused family (the same dispatch as train_impl) stores A1 blocked per
-  // 32-pixel chunk; the wide family and the op-level kernels in HWC
-  size_t unused = 0;
-  const bool blocked =
-      fast_enabled() && srcnn::fused::train_fwd_bwd(net, nullptr, nullptr, w, h, batch, nullptr,
-                                                    nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                    nullptr, nullptr, nullptr, 0, nullptr, true,
-                                                    &unused) == 1;
   // the layout the last step on this workspace wrote (recorded when it ran,
-  // so an srcnn_set_arith since does not change it); else the current dispatch's
+  // so an srcnn_set_arith since does not change it); else the current
+  // dispatch's: the fused family stores A1 per 32-pixel chunk, blocked or in
+  // run order; the wide family and the op-level kernels in HWC
   int layout = srcnn::fused::a1_layout_written(L.A1);
-  if (layout < 0)
-    layout = !blocked ? srcnn::fused::kA1Hwc : srcnn::fused::a1_runs(net, w, h) ? srcnn::fused::kA1Runs
-                                                                                   : srcnn::fused::kA1Blocked;
+  if (layout < 0) layout = step_need(net, w, h, batch).a1_layout;
   int rc = layout == srcnn::fused::kA1Runs ? srcnn::fused::unrun_a1(L.A1, A1, d.w1, d.h1, batch, s)
            : layout == srcnn::fused::kA1Blocked ? srcnn::fused::unblock_a1(L.A1, A1, net->n1, d.w1 * d.h1, batch, s)
                                                 : srcnn_memcpy_d2d(A1, L.A1, d.s1 * batch * sizeof(float), stream);
@@ -759,10 +739,7 @@ size_t srcnn_forward_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t 
   if (net_dims(net, w, h, &d) || batch == 0) return 0;
   size_t generic = align_up(d.s1 * batch * sizeof(float)) + align_up(d.s2 * batch * sizeof(float));
   size_t fused = 0;
-  if (fast_enabled() &&
-      srcnn::fused::forward(net, nullptr, w, h, batch, nullptr, nullptr, nullptr, 0, nullptr, true,
-                            &fused) != 1)
-    fused = 0;
+  if (fast_enabled()) srcnn::fused::forward_plan(net, w, h, batch, &fused);
   return std::max(generic, fused);
 }
 
@@ -777,24 +754,18 @@ int srcnn_forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, 
   if (ws_bytes < need)
     return fail(SRCNN_ERR_WORKSPACE, "forward: workspace %zu B < %zu B", ws_bytes, need);
   if (fast_enabled()) {  // fused gfx950 inference (forward_fused.hip)
-    int rc = srcnn::fused::forward(net, X, w, h, batch, params, out, ws, ws_bytes,
-                                   as_stream(stream), false, nullptr);
+    int rc = srcnn::fused::forward(net, X, w, h, batch, params, out, ws, ws_bytes, as_stream(stream));
     if (rc != 0) return rc < 0 ? rc : tag("fused", SRCNN_OK);
   }
-  size_t off[6];
-  srcnn_net_offsets(net, off);
+  const auto P = srcnn::split_params(params, net);
   float* A1 = static_cast<float*>(ws);
   float* A2 = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(d.s1 * batch * sizeof(float)));
   int rc;
   OpSequence seq;
-  if ((rc = srcnn_conv_fwd(X, A1, params + off[0], params + off[1], w, h, 1, net->n1, net->f1, 1,
-                           batch, stream)))
+  if ((rc = srcnn_conv_fwd(X, A1, P.W1, P.B1, w, h, 1, net->n1, net->f1, 1, batch, stream))) return rc;
+  if ((rc = srcnn_conv_fwd(A1, A2, P.W2, P.B2, d.w1, d.h1, net->n1, net->n2, net->f2, 1, batch, stream)))
     return rc;
-  if ((rc = srcnn_conv_fwd(A1, A2, params + off[2], params + off[3], d.w1, d.h1, net->n1, net->n2,
-                           net->f2, 1, batch, stream)))
-    return rc;
-  return seq.done(srcnn_conv_fwd(A2, out, params + off[4], params + off[5], d.w2, d.h2, net->n2, 1,
-                                 net->f3, 0, batch, stream));
+  return seq.done(srcnn_conv_fwd(A2, out, P.W3, P.B3, d.w2, d.h2, net->n2, 1, net->f3, 0, batch, stream));
 }
 
 // regions of the upscale workspace: padded plane | net output | reduction

@@ -75,6 +75,24 @@ struct Scope {
 
 #define SRCNN_LAUNCH_TRY() SRCNN_HIP_TRY(hipGetLastError())
 
+namespace srcnn {
+// One kernel launch with `lds` bytes of dynamic LDS.  Past the 64 KiB default
+// the kernel's cap is raised first, on every such launch: the attribute is per
+// device, and one process may drive several devices from several threads
+// (cnn train --devices N).  The cap takes no part in occupancy.
+template <typename... P, typename... A>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+      return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+}  // namespace srcnn
+
 // bracket the launches that follow in this scope for the profiler
 #define SRCNN_PROFILE(name, stream) ::srcnn::prof::Scope srcnn_prof_scope_(name, stream)
 

@@ -624,109 +624,129 @@ __global__ __launch_bounds__(256) void fwd_seam_kernel(const float* __restrict__
   }
 }
 
-template <int N1, int N2, int F1, int F3>
-int run_forward(const float* X, uint32_t w, uint32_t h, uint32_t batch, const float* params,
-                float* out, void* ws, size_t ws_bytes, hipStream_t s, bool query_only,
-                size_t* need) {
+template <int N1_, int N2_, int F1_, int F3_>
+struct FwdNet {
+  static constexpr int N1 = N1_, N2 = N2_, F1 = F1_, F3 = F3_;
+  // the default net: fwd_l123x6 is built for it
+  static constexpr bool kDefault = N1 == 64 && N2 == 32 && F1 == 9 && F3 == 5;
+};
+
+// The instantiated nets, once: f(FwdNet<..>{}) of the one that `net` is, else 0.
+// plan, run and preload all dispatch through here.
+template <typename F>
+int with_net(const srcnn_net* net, F&& f) {
+  auto is = [&](auto n) {
+    return net->n1 == (uint32_t)n.N1 && net->n2 == (uint32_t)n.N2 && net->f1 == (uint32_t)n.F1 && net->f2 == 1 &&
+           net->f3 == (uint32_t)n.F3;
+  };
+  if (is(FwdNet<64, 32, 9, 5>{})) return f(FwdNet<64, 32, 9, 5>{});  // reference default
+  if (is(FwdNet<32, 16, 9, 5>{})) return f(FwdNet<32, 16, 9, 5>{});  // example_config.json
+  return 0;
+}
+
+// Everything the forward decides before its first launch.  plan_forward
+// fills it from the shape and the arithmetic alone: no buffer, no HIP call.
+struct FwdPlan {
+  bool x6;  // the default net in split-bf16 products (fwd_l123x6), fixed 24-row regions
+  FwdGeom g;
+  unsigned grid;      // fwd_l123 / fwd_l123x6 blocks
+  size_t lds;         // and their dynamic LDS bytes
+  size_t part_bytes;  // the workspace: the regions' partial sums
+  int seam_bx, seam_rb;  // fwd_seam: threads per block, rows per block
+  dim3 seam_grid;
+};
+
+template <typename NetT>
+bool plan_forward(uint32_t w, uint32_t h, uint32_t batch, int arith, FwdPlan* out) {
+  constexpr int F1 = NetT::F1, F3 = NetT::F3;
+  FwdPlan& p = *out = {};
   const int ow = (int)w - F1 + 1, oh = (int)h - F1 + 1;
-  if (ow < F3 || oh < F3) return 0;
-  // the default net in split-bf16 products (fwd_l123x6), fixed 24-row regions
-  const bool x6 = N1 == 64 && N2 == 32 && F1 == 9 && F3 == 5 && g_arith == 0;
+  if (ow < F3 || oh < F3) return false;
+  p.x6 = NetT::kDefault && arith == 0;
   // region rows: the input tile (32 + f1 - 1) x (rh + f1 - 1) fits the LDS tile,
   // a multiple of the 4 waves
-  int rh = x6 ? kF6Rh : std::min((kFwdXs / (kFwdRW + F1 - 1) - (F1 - 1)) / 4 * 4, kFwdRhMax / 4 * 4);
-  if (rh < F3) return 0;
+  const int rh_f32 = std::min((kFwdXs / (kFwdRW + F1 - 1) - (F1 - 1)) / 4 * 4, kFwdRhMax / 4 * 4);
+  int rh = p.x6 ? kF6Rh : rh_f32;
+  if (rh < F3) return false;
   rh = std::min(rh, oh);
-  FwdGeom g{(int)w, (int)h, ow, oh, rh, (ow + kFwdRW - 1) / kFwdRW, (oh + rh - 1) / rh, (int)batch};
+  const FwdGeom g = p.g = {(int)w, (int)h, ow, oh, rh, (ow + kFwdRW - 1) / kFwdRW, (oh + rh - 1) / rh, (int)batch};
   const long items = (long)g.batch * g.nrx * g.nry;
+  p.grid = (unsigned)std::min<long>(items, p.x6 ? 256 : kFwdGrid);
+  p.lds = p.x6 ? F6Lds::bytes : 0;
   // partial sums of either arithmetic's regions (srcnn_set_arith between the
   // size query and the call needs no new query)
   auto part_bytes = [&](int r) {
     return (size_t)g.batch * g.nrx * ((oh + r - 1) / r) * (r + F3 - 1) * (kFwdRW + F3 - 1) * sizeof(float);
   };
-  size_t pbytes = part_bytes(rh);
-  if (N1 == 64 && N2 == 32 && F1 == 9 && F3 == 5) {
-    const int rh_f32 = std::min(std::min((kFwdXs / (kFwdRW + F1 - 1) - (F1 - 1)) / 4 * 4, kFwdRhMax / 4 * 4), oh);
-    pbytes = std::max({pbytes, part_bytes(rh_f32), part_bytes(std::min(kF6Rh, oh))});
-  }
-  if (query_only) {
-    *need = pbytes;
-    return 1;
-  }
-  if (ws_bytes < pbytes)
-    return fail(SRCNN_ERR_WORKSPACE, "fused forward: workspace %zu B < %zu B", ws_bytes, pbytes);
+  p.part_bytes = part_bytes(rh);
+  if (NetT::kDefault)
+    p.part_bytes = std::max({p.part_bytes, part_bytes(std::min(rh_f32, oh)), part_bytes(std::min(kF6Rh, oh))});
+  const int w3 = ow - F3 + 1, h3 = oh - F3 + 1;
+  p.seam_bx = std::min(256, (w3 + 63) / 64 * 64);
+  // up to 8 rows per block while the grid keeps >= 4096 blocks (4K frame:
+  // 7 rows, 0.0307 -> 0.0267 ms; small frames: 1 row per block)
+  const int nbx = (w3 + p.seam_bx - 1) / p.seam_bx;
+  p.seam_rb = (int)std::max<long>(1, std::min<long>(8, (long)nbx * h3 * batch / 4096));
+  p.seam_grid = dim3((unsigned)nbx, (unsigned)std::min((h3 + p.seam_rb - 1) / p.seam_rb, 65535),
+                     (unsigned)std::min<uint32_t>(batch, 65535));
+  return true;
+}
+
+template <typename NetT>
+int run_forward(const FwdPlan& p, const srcnn_net* net, const float* X, const float* params, float* out, void* ws,
+                size_t ws_bytes, hipStream_t s) {
+  if (ws_bytes < p.part_bytes)
+    return fail(SRCNN_ERR_WORKSPACE, "fused forward: workspace %zu B < %zu B", ws_bytes, p.part_bytes);
   float* part = static_cast<float*>(ws);
-  const float* W1 = params;
-  const float* B1 = W1 + F1 * F1 * N1;
-  const float* W2 = B1 + N1;
-  const float* B2 = W2 + N1 * N2;
-  const float* W3 = B2 + N2;
-  const float* B3 = W3 + F3 * F3 * N2;
+  const auto P = split_params(params, net);
   {
     SRCNN_PROFILE("fwd_l123_mfma", s);
-    if (x6) {
-      hipError_t e = hipFuncSetAttribute((const void*)fwd_l123x6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024);
-      if (e != hipSuccess) return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(fwd_l123x6): %s", hipGetErrorString(e));
-      hipLaunchKernelGGL(fwd_l123x6_kernel, dim3((unsigned)std::min<long>(items, 256)), dim3(512), F6Lds::bytes, s,
-                         X, W1, B1, W2, B2, W3, part, g);
-    } else {
-      hipLaunchKernelGGL((fwd_l123_kernel<N1, N2, F1, F3>), dim3((unsigned)std::min<long>(items, kFwdGrid)),
-                         dim3(256), 0, s, X, W1, B1, W2, B2, W3, part, g);
-    }
-    SRCNN_LAUNCH_TRY();
+    if (int rc = p.x6 ? launch(fwd_l123x6_kernel, dim3(p.grid), dim3(512), p.lds, s, X, P.W1, P.B1, P.W2, P.B2, P.W3, part, p.g)
+                      : launch(fwd_l123_kernel<NetT::N1, NetT::N2, NetT::F1, NetT::F3>, dim3(p.grid), dim3(256), p.lds, s, X,
+                               P.W1, P.B1, P.W2, P.B2, P.W3, part, p.g))
+      return rc;
   }
-  {
-    SRCNN_PROFILE("fwd_l3_seam", s);
-    const int w3 = ow - F3 + 1, h3 = oh - F3 + 1;
-    const int bx = std::min(256, (w3 + 63) / 64 * 64);
-    // up to 8 rows per block while the grid keeps >= 4096 blocks (4K frame:
-    // 7 rows, 0.0307 -> 0.0267 ms; small frames: 1 row per block)
-    const int nbx = (w3 + bx - 1) / bx;
-    const int rb = (int)std::max<long>(1, std::min<long>(8, (long)nbx * h3 * batch / 4096));
-    const dim3 grid((unsigned)nbx, (unsigned)std::min((h3 + rb - 1) / rb, 65535),
-                    (unsigned)std::min<uint32_t>(batch, 65535));
-    hipLaunchKernelGGL((fwd_seam_kernel<F3>), grid, dim3(bx), 0, s, part, B3, out, g, rb);
-    SRCNN_LAUNCH_TRY();
-  }
+  SRCNN_PROFILE("fwd_l3_seam", s);
+  if (int rc = launch(fwd_seam_kernel<NetT::F3>, p.seam_grid, dim3(p.seam_bx), 0, s, part, P.B3, out, p.g, p.seam_rb))
+    return rc;
   return 1;
 }
 
 }  // namespace
+
+bool forward_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, size_t* ws_bytes) {
+  return with_net(net, [&](auto n) {
+    FwdPlan p;
+    if (!plan_forward<decltype(n)>(w, h, batch, g_arith, &p)) return 0;
+    *ws_bytes = p.part_bytes;
+    return 1;
+  });
+}
+
+int forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, uint32_t batch,
+            const float* params, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+  return with_net(net, [&](auto n) {
+    FwdPlan p;
+    if (!plan_forward<decltype(n)>(w, h, batch, g_arith, &p)) return 0;
+    return run_forward<decltype(n)>(p, net, X, params, out, ws, ws_bytes, s);
+  });
+}
+
+int preload_forward(const srcnn_net* net) {
+  return with_net(net, [&](auto n) {
+    using N = decltype(n);
+    const void* k[] = {(const void*)fwd_l123_kernel<N::N1, N::N2, N::F1, N::F3>, (const void*)fwd_seam_kernel<N::F3>,
+                       (const void*)fwd_l123x6_kernel};
+    const int rc = resolve_kernels(k, N::kDefault ? 3 : 2);
+    return rc ? rc : 1;
+  });
+}
 
 int forward_clock(double* ghz) {
   unsigned long long a[1][kClockBlocks][2];
   SRCNN_HIP_TRY(hipMemcpyFromSymbol(a, HIP_SYMBOL(g_clk_fwd), sizeof(a)));
   *ghz = clock_ghz(a[0]);
   return SRCNN_OK;
-}
-
-int preload_forward(const srcnn_net* net) {
-  if (net->f2 != 1) return 0;
-#define SRCNN_FWD_CASE(A, B, C, D)                                                        \
-  if (net->n1 == A && net->n2 == B && net->f1 == C && net->f3 == D) {                    \
-    const void* k[] = {(const void*)fwd_l123_kernel<A, B, C, D>, (const void*)fwd_seam_kernel<D>, \
-                       (const void*)fwd_l123x6_kernel};                                  \
-    int rc = resolve_kernels(k, A == 64 && B == 32 ? 3 : 2);                             \
-    return rc ? rc : 1;                                                                  \
-  }
-  SRCNN_FWD_CASE(64, 32, 9, 5)
-  SRCNN_FWD_CASE(32, 16, 9, 5)
-#undef SRCNN_FWD_CASE
-  return 0;
-}
-
-int forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, uint32_t batch,
-            const float* params, float* out, void* ws, size_t ws_bytes, hipStream_t s,
-            bool query_only, size_t* need) {
-  if (net->f2 != 1) return 0;
-#define SRCNN_FWD_CASE(A, B, C, D)                                                       \
-  if (net->n1 == A && net->n2 == B && net->f1 == C && net->f3 == D)                     \
-    return run_forward<A, B, C, D>(X, w, h, batch, params, out, ws, ws_bytes, s, query_only, need);
-  SRCNN_FWD_CASE(64, 32, 9, 5)  // reference default
-  SRCNN_FWD_CASE(32, 16, 9, 5)  // example_config.json
-#undef SRCNN_FWD_CASE
-  return 0;
 }
 
 }  // namespace fused

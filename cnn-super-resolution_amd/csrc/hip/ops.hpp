@@ -1,5 +1,7 @@
 // ops.hpp -- internal launchers behind srcnn.h (no validation here; abi.cpp
 // validates shapes exactly once, then dispatches generic vs gfx950 paths).
+// The net-level families answer "is this shape served, and what does it
+// need" through their *_plan queries, which take no buffer.
 #pragma once
 
 #include "common.hpp"
@@ -43,28 +45,55 @@ int l1_grad_slabs(const float* X, const float* D1, const float* A1, float* slab,
                   int w, int h, int batch, int grid, hipStream_t s);
 }  // namespace fast
 
+// The buffers of one net-level training step: the caller's tensors, the regions
+// of the training workspace (abi.cpp: train_ws) and the scratch behind them.
+struct StepBuffers {
+  const float *X, *T, *params;
+  float *grads, *sq_err;
+  float *A1, *D1, *A2, *D2, *A3, *D3;
+  float* slab;
+  size_t slab_bytes;
+};
+// What a family's step needs: slab bytes, and the layout it writes A1 in (fused::kA1*).
+struct StepNeed {
+  size_t slab_bytes;
+  int a1_layout;
+};
+// The flat parameter (or gradient) buffer [W1|B1|W2|B2|W3|B3] by layer.
+template <typename T>
+struct LayerPtrs {
+  T *W1, *B1, *W2, *B2, *W3, *B3;
+};
+template <typename T>
+inline LayerPtrs<T> split_params(T* p, const srcnn_net* net) {
+  size_t off[6];
+  srcnn_net_offsets(net, off);
+  return {p + off[0], p + off[1], p + off[2], p + off[3], p + off[4], p + off[5]};
+}
+
 // Fused training step for nets with a 1x1 middle layer (train_fused.hip).
-// Returns 1 when the net/shape is specialised (step enqueued, or with
-// query_only the slab workspace size written to *need), 0 when not.
 namespace fused {
 struct SlabUpdate;
 struct LazyUpdate;
-// With `up` (srcnn_train_step) the slab reduction also applies the SGD
-// update to every parameter it completes and returns 2 instead of 1 when it
-// did (layer 3 on l3_delta, so the slabs cover all parameters).  With `lz`
-// (srcnn_train_fwd_bwd_lazy) the step first applies lz's pending update
-// inside l12 (lz->batch > 0; `params` is then ignored and the step runs on
-// lz->Po) and OVERWRITES grads instead of accumulating.
-int train_fwd_bwd(const srcnn_net* net, const float* X, const float* T, uint32_t w, uint32_t h,
-                  uint32_t batch, const float* params, float* grads, float* sq_err, float* A1,
-                  float* A2, float* D2, float* A3, float* D3, float* slab, size_t slab_bytes,
-                  hipStream_t s, bool query_only, size_t* need, const SlabUpdate* up = nullptr,
-                  const LazyUpdate* lz = nullptr);
-// Fused inference (forward_fused.hip): 1 when specialised (with query_only:
-// workspace bytes in *need), 0 when not.
+// Whether the family serves this net / tile under the current arithmetic, and
+// if so what its step needs (else *need is left alone): the step's StepPlan.
+bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, StepNeed* need);
+// The step: 1 when enqueued, 0 when the family does not serve the shape,
+// < 0 on error.  With `up` (srcnn_train_step, else null) the
+// slab reduction also applies the SGD update to every parameter it completes
+// and returns 2 instead of 1 when it did (layer 3 on l3_delta, so the slabs
+// cover all parameters).  With `lz` (srcnn_train_fwd_bwd_lazy, else null) the
+// step first applies lz's pending update inside l12 (lz->batch > 0; b.params
+// is then ignored and the step runs on lz->Po) and OVERWRITES grads instead
+// of accumulating.  b.D1 is not used.
+int train_fwd_bwd(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, const StepBuffers& b,
+                  hipStream_t s, const SlabUpdate* up, const LazyUpdate* lz);
+// Fused inference (forward_fused.hip): forward_plan tells whether the net is
+// served and the workspace bytes (FwdPlan); forward returns 1 when it ran,
+// 0 when the net is not served, < 0 on error.
+bool forward_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, size_t* ws_bytes);
 int forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, uint32_t batch,
-            const float* params, float* out, void* ws, size_t ws_bytes, hipStream_t s,
-            bool query_only, size_t* need);
+            const float* params, float* out, void* ws, size_t ws_bytes, hipStream_t s);
 // Deterministic slab reduction shared by the fused families and the op-level
 // gradient kernels: for every segment, dst[i] += sum_{b < nslab}
 // slab[b * stride + i] (i < P), summed in block order.
@@ -145,10 +174,6 @@ __device__ __forceinline__ void lazy_write_slice(const LazyUpdate& u) {
 }
 // held-clock probes (common.hpp): slot 0 l12_fwd, 1 l3_delta, 2 d1_grad12
 int train_clock(int slot, double* ghz);
-// the split-bf16 step (l12x6) stores A1 in run order, transposed per chunk:
-// a1_runs tells whether the fused step takes that path for this net / tile,
-// a1_chunks the A1 chunks per sample either path needs, unrun_a1 converts
-bool a1_runs(const srcnn_net* net, uint32_t w, uint32_t h);
 // the layout the last training step of this thread wrote into the A1 region
 // at `A1` (kA1Runs, kA1Blocked, kA1Hwc), or -1 if it wrote none there; so
 // srcnn_train_activations follows the arithmetic the step ran with, whatever
@@ -156,6 +181,9 @@ bool a1_runs(const srcnn_net* net, uint32_t w, uint32_t h);
 enum { kA1Blocked = 0, kA1Runs = 1, kA1Hwc = 2 };
 void note_a1_layout(const float* A1, int layout);
 int a1_layout_written(const float* A1);
+// the split-bf16 step (l12x6) stores A1 in run order, transposed per chunk
+// (kA1Runs): a1_chunks is the A1 chunks per sample either layout needs,
+// unrun_a1 converts to HWC
 size_t a1_chunks(uint32_t ow, uint32_t oh);
 int unrun_a1(const float* A1t, float* A1, uint32_t ow, uint32_t oh, uint32_t batch, hipStream_t s);
 // the fused step's blocked A1 (l12_fwd_kernel) -> reference HWC [batch][npx][n1]
@@ -169,14 +197,13 @@ int forward_clock(double* ghz);
 
 // Training step for nets with a spatial middle layer (train_wide.hip), e.g.
 // the wide config n1=128, n2=64, f1=9, f2=5, f3=5: per-stage MFMA kernels over
-// the reference-layout A1 / D1 / A2 / D2 buffers.  Same contract as
-// fused::train_fwd_bwd.
+// the reference-layout A1 / D1 / A2 / D2 buffers (A1 in kA1Hwc; b.D3 is not
+// used).  Same contracts as fused::train_plan (WidePlan) and
+// fused::train_fwd_bwd; with `up` the update always rides along (returns 2).
 namespace wide {
-int train_fwd_bwd(const srcnn_net* net, const float* X, const float* T, uint32_t w, uint32_t h,
-                  uint32_t batch, const float* params, float* grads, float* sq_err, float* A1,
-                  float* D1, float* A2, float* D2, float* A3, float* slab, size_t slab_bytes,
-                  hipStream_t s, bool query_only, size_t* need,
-                  const fused::SlabUpdate* up = nullptr);
+bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, StepNeed* need);
+int train_fwd_bwd(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, const StepBuffers& b,
+                  hipStream_t s, const fused::SlabUpdate* up);
 int preload(const srcnn_net* net);
 // op-level launchers of the 5x5 128 <-> 64 middle layer (same contract as
 // the fast::try_* functions: 1 handled, 0 not this shape, < 0 error)

@@ -886,291 +886,245 @@ int reduce_slabs(const SlabSeg* segs, int nseg, hipStream_t s, const SlabUpdate*
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <int N1, int N2, int F1, int F3>
+template <int N1_, int N2_, int F1_, int F3_>
 struct Net {
+  static constexpr int N1 = N1_, N2 = N2_, F1 = F1_, F3 = F3_;
   static constexpr int P12 = F1 * F1 * N1 + N1 + N1 * N2 + N2;
   static constexpr int P3 = F3 * F3 * N2 + 1;
+  // layers 1-2 of the default net: the split-bf16 pair and d1c are built for them
+  static constexpr bool kDefault12 = N1 == 64 && N2 == 32 && F1 == 9;
 };
+
+// The instantiated nets, once: f(Net<..>{}) of the one that `net` is, else 0.
+// plan, run and preload all dispatch through here.
+template <typename F, typename... Ns>
+static int first_net(const srcnn_net* net, F&& f, Ns... ns) {
+  int rc = 0;
+  auto is = [&](auto n) {
+    return net->n1 == (uint32_t)n.N1 && net->n2 == (uint32_t)n.N2 && net->f1 == (uint32_t)n.F1 &&
+           net->f2 == 1 && net->f3 == (uint32_t)n.F3;
+  };
+  (void)((is(ns) && (rc = f(ns), true)) || ...);
+  return rc;
+}
+template <typename F>
+static int with_net(const srcnn_net* net, F&& f) {
+  return first_net(net, f, Net<64, 32, 9, 5>{},  // reference default (BASELINE.json configs[1])
+                   Net<32, 16, 9, 5>{},          // example_config.json
+                   Net<64, 32, 9, 3>{}, Net<32, 16, 9, 3>{});  // the same with a 3x3 last layer
+}
 
 static int grid_for_batch(uint32_t batch, int cap) { return (int)std::min<uint32_t>(batch, cap); }
 
-template <int F3, bool kD3Out>
-static int launch_l3r(const float* A2, const float* T, const float* W3, const float* B3, float* D2,
-                      float* slab3, float* sqs, float* A3, uint32_t* M2, const L3Geom& lg, int grid,
-                      size_t lds, hipStream_t s) {
-  // 70 KB exceeds the 64 KiB default dynamic LDS (set per launch: see launch_l3)
-  hipError_t e = hipFuncSetAttribute((const void*)l3r_delta_kernel<F3, kD3Out>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  if (e != hipSuccess)
-    return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(l3r_delta): %s", hipGetErrorString(e));
-  hipLaunchKernelGGL((l3r_delta_kernel<F3, kD3Out>), dim3(grid), dim3(kL3RThreads), lds, s, A2, T, W3, B3,
-                     D2, slab3, sqs, A3, M2, lg);
-  SRCNN_LAUNCH_TRY();
-  return SRCNN_OK;
-}
+// Everything the step decides before its first launch.  plan_step fills it
+// from the shape and the arithmetic alone: no buffer, no HIP call.
+struct StepPlan {
+  int ow, oh, w3, h3;
+  // x6: split-bf16 l12x6 + d1x6.  l3r / l3_fused: layer 3 by l3r_delta, else
+  // by l3_delta, else (not l3_fused) by the op-level kernels.  d3mode: l3r
+  // leaves delta3 and layer 2's relu' mask in the D2 region and d1x6 forms
+  // delta2 (d1x6.hpp kD3).  kD1c: the fp32 delta1 kernel is d1c, split over
+  // d1c_parts ranges of chunks per sample.
+  bool x6, l3r, l3_fused, d3mode, kD1c;
+  int d1c_parts;
+  RunGeom rg;
+  int g12, g3, gd;           // grids of l12, layer 3 and delta1 (one slab per block of the last two)
+  size_t lds12, lds3, ldsd;  // their dynamic LDS bytes
+  size_t s12, s3, ssq;       // slab regions in floats: layers 1-2 | layer 3 | squared error
+  size_t bytes;              // the three in bytes
+  size_t m2_off;             // d3mode: dwords from D2 to the mask (delta3 first, 256-B aligned)
+  int a1_layout;             // what l12 writes: kA1Runs or kA1Blocked
+};
 
-// the A1 region and layout (1 = run order, 0 = blocked) this thread's last
-// fused step wrote (a1_layout_written: srcnn_train_activations)
-static thread_local const float* t_a1_region = nullptr;
-static thread_local int t_a1_layout = -1;
-
-// the split-bf16 pair (l12x6 + d1x6) serves the default net where both fit
-static bool x6_active(int n1, int n2, int f1, uint32_t w, uint32_t h) {
-  return n1 == 64 && n2 == 32 && f1 == 9 && g_arith == 0 && l12x6_fits(w, h) && d1x6_fits(w, h);
-}
-
-// 78 KB of LDS for 33x33 tiles: two blocks per CU
-static int launch_l12x6(const float* X, const float* W1, const float* B1, const float* W2, const float* B2,
-                        float* A1, float* A2, const Geom& g, const RunGeom& rg, const LazyUpdate* lz, int grid,
-                        hipStream_t s) {
-  const void* k = lz ? (const void*)l12x6_fwd_kernel<true> : (const void*)l12x6_fwd_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-  if (e != hipSuccess) return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(l12x6_fwd): %s", hipGetErrorString(e));
-  const size_t lds = X6Lds(g.W, g.H).bytes;
-  if (lz)
-    hipLaunchKernelGGL((l12x6_fwd_kernel<true>), dim3(grid), dim3(256), lds, s, X, W1, B1, W2, B2, A1, A2, g, rg,
-                       *lz);
-  else
-    hipLaunchKernelGGL((l12x6_fwd_kernel<false>), dim3(grid), dim3(256), lds, s, X, W1, B1, W2, B2, A1, A2, g, rg,
-                       LazyUpdate{});
-  SRCNN_LAUNCH_TRY();
-  return SRCNN_OK;
-}
-
-// kD3: D2 holds delta3 and M2 layer 2's relu' mask (l3r_delta_kernel<F3,
-// true>) and d1x6 forms delta2; A2 is not read then
-static int launch_d1x6(bool kD3, const float* X, const float* A1, const float* D2, const float* A2,
-                       const uint32_t* M2, const float* W2, const float* W3, float* slab, const Geom& g,
-                       const RunGeom& rg, const D3Geom& dg, int grid, hipStream_t s) {
-  const void* k = kD3 ? (const void*)d1x6_grad12_kernel<true> : (const void*)d1x6_grad12_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(d1x6_grad12): %s", hipGetErrorString(e));
-  const size_t lds = D6Lds(g.W, g.H, rg, kD3).bytes;
-  if (kD3)
-    hipLaunchKernelGGL(d1x6_grad12_kernel<true>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, M2, W2, W3, slab, g,
-                       rg, dg);
-  else
-    hipLaunchKernelGGL(d1x6_grad12_kernel<false>, dim3(grid), dim3(256), lds, s, X, A1, D2, A2, M2, W2, W3, slab,
-                       g, rg, dg);
-  SRCNN_LAUNCH_TRY();
-  return SRCNN_OK;
-}
-
-template <int N2, int F3>
-static int launch_l3(const float* A2, const float* T, const float* W3, const float* B3, float* D2,
-                     float* slab3, float* sqs, float* A3, const L3Geom& lg, int grid, size_t lds,
-                     hipStream_t s) {
-  // two A2 tiles exceed the 64 KiB default dynamic LDS.  Set on every launch:
-  // the attribute is per device, and one process may drive several devices
-  // from several threads (cnn train --devices N)
-  hipError_t e = hipFuncSetAttribute((const void*)l3_delta_kernel<N2, F3>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess)
-    return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(l3_delta): %s", hipGetErrorString(e));
-  hipLaunchKernelGGL((l3_delta_kernel<N2, F3>), dim3(grid), dim3(kL3Threads), lds, s, A2, T, W3,
-                     B3, D2, slab3, sqs, A3, lg);
-  SRCNN_LAUNCH_TRY();
-  return SRCNN_OK;
-}
-
-// Returns 1 if the shape is specialised (and the step was enqueued), 0 if
-// not (caller falls back to the op-by-op path), <0 on error.
-template <int N1, int N2, int F1, int F3>
-static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t batch,
-               const float* params, float* grads, float* sq_err, float* A1, float* A2, float* D2,
-               float* A3, float* D3, float* slab, size_t slab_bytes, hipStream_t s, bool query_only,
-               size_t* need, const SlabUpdate* up, const LazyUpdate* lz) {
-  using NetT = Net<N1, N2, F1, F3>;
-  const int ow = w - F1 + 1, oh = h - F1 + 1;
-  const int w3 = ow - F3 + 1, h3 = oh - F3 + 1;
-  if ((int)(w * h) > kXsMax || (int)w > kL12S || (int)h > kL12Rows || w3 <= 0 || h3 <= 0) return 0;
+template <typename NetT>
+static bool plan_step(uint32_t w, uint32_t h, uint32_t batch, int arith, StepPlan* out) {
+  constexpr int N2 = NetT::N2, F1 = NetT::F1, F3 = NetT::F3;
+  StepPlan& p = *out = {};
+  const int ow = p.ow = w - F1 + 1, oh = p.oh = h - F1 + 1;
+  const int w3 = p.w3 = ow - F3 + 1, h3 = p.h3 = oh - F3 + 1;
+  if ((int)(w * h) > kXsMax || (int)w > kL12S || (int)h > kL12Rows || w3 <= 0 || h3 <= 0) return false;
   // l3_delta holds two A2 tiles in LDS: up to 640 A2 pixels (33x33 tiles at
   // f1 = 9).  Larger tiles (e.g. the reference's 36x36 samples, profile.py:7)
   // keep l12 and d1 and run layer 3 through the op-level kernels instead
   // (ops_fast.hip: L3 forward, last delta, delta2, gW3 over HWC A2 / A3 / D3).
   // n2 = 32: l3r (A2 in registers, two blocks per CU) where the tile fits it
-  const bool l3r = N2 == 32 && l3r_fits<F3>(ow, oh, w3, h3);
-  const size_t lds3 = l3r ? L3RLds<F3>(ow, oh).bytes() : l3_lds_bytes<N2, F3>(ow, oh);
+  p.l3r = N2 == 32 && l3r_fits<F3>(ow, oh, w3, h3);
+  p.lds3 = p.l3r ? L3RLds<F3>(ow, oh).bytes() : l3_lds_bytes<N2, F3>(ow, oh);
   // (n2 = 32 tiles past l3r's 512 outputs, e.g. f3 = 3 on 33x33: l3_delta)
-  const bool l3_fused =
-      l3r || (lds3 <= 160 * 1024 && w3 * h3 <= kL3MaxOut &&
-              ((ow * oh + 15) / 16 + kL3Threads / 64 - 1) / (kL3Threads / 64) <= L3Lds<N2, F3>::kUnitsPerWave);
-  const int g12 = grid_for_batch(batch, kL12Grid);
-  // split-bf16 products (l12x6.hpp, d1x6.hpp) for the default net
-  const bool x6 = x6_active(N1, N2, F1, w, h);
-  const RunGeom rg = run_geom(ow, oh);
+  p.l3_fused =
+      p.l3r || (p.lds3 <= 160 * 1024 && w3 * h3 <= kL3MaxOut &&
+                ((ow * oh + 15) / 16 + kL3Threads / 64 - 1) / (kL3Threads / 64) <= L3Lds<N2, F3>::kUnitsPerWave);
+  p.g12 = grid_for_batch(batch, kL12Grid);
+  // split-bf16 products (l12x6.hpp, d1x6.hpp) serve the default net where both fit
+  p.x6 = NetT::kDefault12 && arith == 0 && l12x6_fits(w, h) && d1x6_fits(w, h);
+  p.a1_layout = p.x6 ? kA1Runs : kA1Blocked;
+  p.rg = run_geom(ow, oh);
   // l3r: up to 2 resident blocks per CU; between 256 and 1024 samples keep
   // two samples per block, so the second sample's A2 loads run under the first
   // one's delta2 phase (512 tiles: l3 0.0306 -> 0.0295 ms; at batch 4096 a
   // 256-block grid is slower, 0.155 -> 0.167 ms; profiles/r04_ab_l3rgrid)
   const int b3 = (int)batch;
-  const int g3 = l3r ? std::min(kL3RGrid, std::max(std::min(b3, 256), (b3 + 1) / 2))
-                     : grid_for_batch(batch, 256);
-  const bool kD1c = N1 == 64 && N2 == 32 && F1 == 9 && d1c_fits(w, h);
+  p.g3 = p.l3r ? std::min(kL3RGrid, std::max(std::min(b3, 256), (b3 + 1) / 2)) : grid_for_batch(batch, 256);
+  p.kD1c = NetT::kDefault12 && d1c_fits(w, h);
   // d1c below kD1cGrid samples: each sample's chunks split into `parts`
   // ranges (work items), so the grid still fills every CU's 4 block slots
   const int nch1 = (ow * oh + 31) / 32;
-  int d1c_parts = kD1c ? std::max(1, std::min({4, nch1, kD1cGrid / (int)std::max<uint32_t>(batch, 1)})) : 1;
-  while (d1c_parts > 1 && (d1c_parts - 1) * ((nch1 + d1c_parts - 1) / d1c_parts) >= nch1)
-    d1c_parts--;  // every part holds at least one chunk (the kernel's DMA pipeline assumes it)
-  const int gd6 = grid_for_batch(batch, 256);  // d1x6: one slab per block
-  // split-bf16 with l3r: delta2 is formed in d1x6 from l3r's delta3 (d1x6.hpp kD3)
-  const bool d3mode = x6 && l3r && F3 <= 5 && d1x6_fits(w, h, true) && l3r_d3_fits<F3>(ow, oh);
-  const int gdf = kD1c ? (int)std::min<size_t>((size_t)batch * d1c_parts, kD1cGrid) : grid_for_batch(batch, 512);
-  const int gd = x6 ? gd6 : gdf;
+  p.d1c_parts = p.kD1c ? std::max(1, std::min({4, nch1, kD1cGrid / (int)std::max<uint32_t>(batch, 1)})) : 1;
+  while (p.d1c_parts > 1 && (p.d1c_parts - 1) * ((nch1 + p.d1c_parts - 1) / p.d1c_parts) >= nch1)
+    p.d1c_parts--;  // every part holds at least one chunk (the kernel's DMA pipeline assumes it)
+  // split-bf16 with l3r: delta2 is formed in d1x6 from l3r's delta3, where
+  // delta3 and the mask (one dword per A2 pixel) fit the region sized for
+  // delta2 (ow * oh * N2 floats per sample)
+  p.m2_off = ((size_t)batch * w3 * h3 + 63) & ~(size_t)63;
+  p.d3mode = p.x6 && p.l3r && F3 <= 5 && d1x6_fits(w, h, true) && l3r_d3_fits<F3>(ow, oh) &&
+             p.m2_off + (size_t)batch * ow * oh <= (size_t)batch * ow * oh * N2;
+  const int gd6 = grid_for_batch(batch, 256);  // d1x6
+  const int gdf = p.kD1c ? (int)std::min<size_t>((size_t)batch * p.d1c_parts, kD1cGrid) : grid_for_batch(batch, 512);
+  p.gd = p.x6 ? gd6 : gdf;
+  p.lds12 = p.x6 ? X6Lds(w, h).bytes : 0;
+  p.ldsd = p.x6 ? D6Lds(w, h, p.rg, p.d3mode).bytes : p.kD1c ? d1c_lds_bytes(w, h) : 0;
   // (the workspace holds either arithmetic's slabs: srcnn_set_arith between
   // the size query and the step needs no new query)
-  const size_t s12 = (size_t)std::max(gd6, gdf) * NetT::P12;
-  size_t s3 = (size_t)g3 * NetT::P3, ssq = g3;  // gW3 slabs, squared-error slabs
-  if (!l3_fused) {  // the op-level gW3 slabs; the same space serves the squared-error reduction
-    s3 = fast::grad_workspace_bytes(N2, 1, F3, w3, h3, batch) / sizeof(float);
-    if (s3 == 0) return 0;  // the op-level layer-3 kernels do not take this tile either
-    s3 = std::max<size_t>(s3, reduce_blocks((size_t)batch * w3 * h3) + 1);
-    ssq = 0;
+  p.s12 = (size_t)std::max(gd6, gdf) * NetT::P12;
+  p.s3 = (size_t)p.g3 * NetT::P3;  // gW3 slabs
+  p.ssq = p.g3;
+  if (!p.l3_fused) {  // the op-level gW3 slabs; the same space serves the squared-error reduction
+    p.s3 = fast::grad_workspace_bytes(N2, 1, F3, w3, h3, batch) / sizeof(float);
+    if (p.s3 == 0) return false;  // the op-level layer-3 kernels do not take this tile either
+    p.s3 = std::max<size_t>(p.s3, reduce_blocks((size_t)batch * w3 * h3) + 1);
+    p.ssq = 0;
   }
-  const size_t bytes = (s12 + s3 + ssq) * sizeof(float);
-  if (query_only) {
-    *need = bytes;
-    return 1;
-  }
-  if (slab_bytes < bytes)
-    return fail(SRCNN_ERR_WORKSPACE, "fused train step: slab workspace %zu B < %zu B", slab_bytes, bytes);
-  float* slab12 = slab;
-  float* slab3 = slab12 + s12;
-  float* sqs = slab3 + s3;
+  p.bytes = (p.s12 + p.s3 + p.ssq) * sizeof(float);
+  return true;
+}
+
+// the A1 region and layout this thread's last step wrote (a1_layout_written:
+// srcnn_train_activations)
+static thread_local const float* t_a1_region = nullptr;
+static thread_local int t_a1_layout = -1;
+
+// Carves the slab and launches in order; every decision comes from the plan.
+template <typename NetT>
+static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch,
+               const StepBuffers& b, hipStream_t s, const SlabUpdate* up, const LazyUpdate* lz) {
+  constexpr int N1 = NetT::N1, N2 = NetT::N2, F1 = NetT::F1, F3 = NetT::F3;
+  if (b.slab_bytes < p.bytes)
+    return fail(SRCNN_ERR_WORKSPACE, "fused train step: slab workspace %zu B < %zu B", b.slab_bytes, p.bytes);
+  float* slab12 = b.slab;
+  float* slab3 = slab12 + p.s12;
+  float* sqs = slab3 + p.s3;
+  const float *X = b.X, *T = b.T;
+  float *grads = b.grads, *A1 = b.A1, *A2 = b.A2, *D2 = b.D2, *A3 = b.A3;
   // lazy: l12 applies the pending update and the step runs on lz->Po
   const bool lazy = lz && lz->batch > 0.0f;
-  if (lazy) params = lz->Po;
-  // flat parameter layout [W1|B1|W2|B2|W3|B3]
-  const float* W1 = params;
-  const float* B1 = W1 + F1 * F1 * N1;
-  const float* W2 = B1 + N1;
-  const float* B2 = W2 + N1 * N2;
-  const float* W3 = B2 + N2;
-  const float* B3 = W3 + F3 * F3 * N2;
-  Geom g{(int)w, (int)h, ow, oh, (int)batch};
+  const LazyUpdate lu = lazy ? *lz : LazyUpdate{};
+  const auto P = split_params(lazy ? lz->Po : b.params, net);
+  const int ow = p.ow, oh = p.oh, w3 = p.w3, h3 = p.h3;
+  const Geom g{(int)w, (int)h, ow, oh, (int)batch};
   {
     SRCNN_PROFILE("l12_fwd_mfma", s);
-    kernels_note(x6 ? (lazy ? "l12x6_fwd_lazy" : "l12x6_fwd") : lazy ? "l12_fwd_lazy" : "l12_fwd");
-    note_a1_layout(A1, x6 ? kA1Runs : kA1Blocked);
-    if (x6) {
-      if (int rc = launch_l12x6(X, W1, B1, W2, B2, A1, A2, g, rg, lazy ? lz : nullptr, g12, s)) return rc;
-    } else if (lazy)
-      hipLaunchKernelGGL((l12_fwd_kernel<N1, N2, F1, true>), dim3(g12), dim3(256), 0, s, X, W1,
-                         B1, W2, B2, A1, A2, g, *lz);
-    else
-      hipLaunchKernelGGL((l12_fwd_kernel<N1, N2, F1>), dim3(g12), dim3(256), 0, s, X, W1,
-                         B1, W2, B2, A1, A2, g, LazyUpdate{});
-    if (!x6) SRCNN_LAUNCH_TRY();
+    kernels_note(p.x6 ? (lazy ? "l12x6_fwd_lazy" : "l12x6_fwd") : lazy ? "l12_fwd_lazy" : "l12_fwd");
+    note_a1_layout(A1, p.a1_layout);
+    const dim3 grid(p.g12), blk(256);
+    // l12x6: 78 KB of LDS for 33x33 tiles, two blocks per CU
+    int rc = p.x6 ? (lazy ? launch(l12x6_fwd_kernel<true>, grid, blk, p.lds12, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, p.rg, lu)
+                          : launch(l12x6_fwd_kernel<false>, grid, blk, p.lds12, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, p.rg, lu))
+                  : (lazy ? launch(l12_fwd_kernel<N1, N2, F1, true>, grid, blk, 0, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, lu)
+                          : launch(l12_fwd_kernel<N1, N2, F1>, grid, blk, 0, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, lu));
+    if (rc) return rc;
   }
   // lazy, layer 3 on the op-level kernels: they accumulate, so their
   // gradient segment starts from zero (after l12 has read the pending one)
-  if (lz && !l3_fused)
+  if (lz && !p.l3_fused)
     SRCNN_HIP_TRY(hipMemsetAsync(grads + NetT::P12, 0, NetT::P3 * sizeof(float), s));
-  L3Geom lg{(int)w, (int)h, ow, oh, w3, h3, (int)batch};
-  // delta3 mode: the D2 region (sized for delta2: ow * oh * N2 floats per
-  // sample) holds delta3 (w3 * h3 floats per sample) and after it, 256-B
-  // aligned, layer 2's relu' mask (one dword per A2 pixel), written by l3r
-  // and read by d1x6
-  uint32_t* M2 = nullptr;
-  if (d3mode) {
-    const size_t moff = ((size_t)batch * w3 * h3 + 63) & ~(size_t)63;
-    if (moff + (size_t)batch * ow * oh > (size_t)batch * ow * oh * N2)
-      return fail(SRCNN_ERR_INVALID, "fused step: delta3 and the relu' mask exceed the delta2 region");
-    M2 = reinterpret_cast<uint32_t*>(D2) + moff;
-  }
-  if (l3_fused) {
+  const L3Geom lg{(int)w, (int)h, ow, oh, w3, h3, (int)batch};
+  uint32_t* M2 = p.d3mode ? reinterpret_cast<uint32_t*>(D2) + p.m2_off : nullptr;
+  if (p.l3_fused) {
     SRCNN_PROFILE("l3_delta_fused", s);
-    kernels_note(!l3r ? "l3_delta" : d3mode ? "l3r_d3" : "l3r_delta");
-    int rc = !l3r    ? launch_l3<N2, F3>(A2, T, W3, B3, D2, slab3, sqs, A3, lg, g3, lds3, s)
-             : d3mode ? launch_l3r<F3, true>(A2, T, W3, B3, D2, slab3, sqs, A3, M2, lg, g3, lds3, s)
-                      : launch_l3r<F3, false>(A2, T, W3, B3, D2, slab3, sqs, A3, nullptr, lg, g3, lds3, s);
+    kernels_note(!p.l3r ? "l3_delta" : p.d3mode ? "l3r_d3" : "l3r_delta");
+    const dim3 grid(p.g3);
+    int rc = !p.l3r ? launch(l3_delta_kernel<N2, F3>, grid, dim3(kL3Threads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, lg)
+             : p.d3mode ? launch(l3r_delta_kernel<F3, true>, grid, dim3(kL3RThreads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, M2, lg)
+                        : launch(l3r_delta_kernel<F3, false>, grid, dim3(kL3RThreads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, M2, lg);
     if (rc) return rc;
   } else {
     // ConfigBasedDataPipeline.cpp:200-323 for layer 3 on the op-level kernels
     kernels_note("l3_op_level");
-    const int rf = fast::try_conv_fwd(A2, A3, W3, B3, ow, oh, N2, 1, F3, 0, batch, s);
+    const int rf = fast::try_conv_fwd(A2, A3, P.W3, P.B3, ow, oh, N2, 1, F3, 0, batch, s);
     if (rf != 1) return rf < 0 ? rf : fail(SRCNN_ERR_INVALID, "fused step: no layer-3 kernel for %dx%d", ow, oh);
-    if (sq_err)
-      if (int rc = reduce(2, A3, T, (size_t)batch * w3 * h3, w, h, w3, h3, sq_err, 1, slab3,
-                          s3 * sizeof(float), s))
+    if (b.sq_err)
+      if (int rc = reduce(2, A3, T, (size_t)batch * w3 * h3, w, h, w3, h3, b.sq_err, 1, slab3,
+                          p.s3 * sizeof(float), s))
         return rc;
-    if (int rc = generic::last_delta(T, A3, D3, w, h, w3, h3, batch, s)) return rc;
-    const int rd = fast::try_conv_delta(D3, A2, D2, W3, F3, N2, 1, ow, oh, batch, s);
+    if (int rc = generic::last_delta(T, A3, b.D3, w, h, w3, h3, batch, s)) return rc;
+    const int rd = fast::try_conv_delta(b.D3, A2, D2, P.W3, F3, N2, 1, ow, oh, batch, s);
     if (rd != 1) return rd < 0 ? rd : fail(SRCNN_ERR_INVALID, "fused step: no delta2 kernel for %dx%d", ow, oh);
-    const int rg = fast::try_conv_grad_acc(A2, D3, grads + NetT::P12, grads + NetT::P12 + NetT::P3 - 1, N2, 1,
-                                           F3, w3, h3, batch, slab3, s3 * sizeof(float), s);
+    const int rg = fast::try_conv_grad_acc(A2, b.D3, grads + NetT::P12, grads + NetT::P12 + NetT::P3 - 1, N2, 1,
+                                           F3, w3, h3, batch, slab3, p.s3 * sizeof(float), s);
     if (rg != 1) return rg < 0 ? rg : fail(SRCNN_ERR_INVALID, "fused step: no gW3 kernel for %dx%d", ow, oh);
   }
   {
     SRCNN_PROFILE("delta1_grad12_fused", s);
-    kernels_note(x6 ? (d3mode ? "d1x6_d3" : "d1x6_grad12") : kD1c ? "d1c_grad12" : "d1_grad12");
-    if (x6) {
-      const D3Geom dg{w3, h3, F3};
-      if (int rc = launch_d1x6(d3mode, X, A1, D2, A2, M2, W2, W3, slab12, g, rg, dg, gd6, s)) return rc;
-    } else if (kD1c)
-      hipLaunchKernelGGL((d1c_grad12_kernel<(F1 == 9 ? F1 : 9)>), dim3(gd), dim3(256 * kD1cTeams), d1c_lds_bytes(w, h),
-                         s, X, A1, D2, W2, slab12, g, d1c_xs_floats(h), d1c_parts);
-    else
-      hipLaunchKernelGGL((d1_grad12_kernel<N1, N2, F1>), dim3(gd), dim3(256), 0, s, X, A1, D2, W2,
-                         slab12, g);
-    if (!x6) SRCNN_LAUNCH_TRY();
-  }
-  {
-    SRCNN_PROFILE("slab_reduce", s);
-    kernels_note(up && l3_fused ? "slab_reduce_update" : "slab_reduce");
-    const SlabSeg segs[3] = {{slab12, grads, gd, NetT::P12, 0},
-                             {slab3, grads + NetT::P12, g3, NetT::P3, 0},
-                             {sqs, sq_err, g3, 1, 0}};
-    // with `up`, segments 0 and 1 are every parameter: the update rides along
-    SlabUpdate u{};
-    if (up && l3_fused) {
-      u = *up;
-      u.nseg = 2;
-    }
-    // lazy: the slabs are this step's whole gradient (assigned, not added)
-    const int assign = lz ? (l3_fused ? 2 : 1) : 0;
-    int rc = l3_fused ? reduce_slabs(segs, sq_err ? 3 : 2, s, &u, assign) : reduce_slabs(segs, 1, s, nullptr, assign);
+    kernels_note(p.x6 ? (p.d3mode ? "d1x6_d3" : "d1x6_grad12") : p.kD1c ? "d1c_grad12" : "d1_grad12");
+    const dim3 grid(p.gd), blk(256);
+    const D3Geom dg{w3, h3, F3};
+    // d1x6<true>: D2 holds delta3 and M2 the mask; A2 is not read then
+    int rc = p.x6 ? (p.d3mode ? launch(d1x6_grad12_kernel<true>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg)
+                              : launch(d1x6_grad12_kernel<false>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg))
+             : p.kD1c ? launch(d1c_grad12_kernel<9>, grid, dim3(256 * kD1cTeams), p.ldsd, s, X, A1, D2, P.W2, slab12, g,
+                               d1c_xs_floats(h), p.d1c_parts)
+                      : launch(d1_grad12_kernel<N1, N2, F1>, grid, blk, 0, s, X, A1, D2, P.W2, slab12, g);
     if (rc) return rc;
-    if (up && l3_fused) return 2;
   }
-  return 1;
+  SRCNN_PROFILE("slab_reduce", s);
+  const bool update = up && p.l3_fused;
+  kernels_note(update ? "slab_reduce_update" : "slab_reduce");
+  const SlabSeg segs[3] = {{slab12, grads, p.gd, NetT::P12, 0},
+                           {slab3, grads + NetT::P12, p.g3, NetT::P3, 0},
+                           {sqs, b.sq_err, p.g3, 1, 0}};
+  // with `up`, segments 0 and 1 are every parameter: the update rides along
+  SlabUpdate u{};
+  if (update) {
+    u = *up;
+    u.nseg = 2;
+  }
+  // lazy: the slabs are this step's whole gradient (assigned, not added)
+  const int assign = lz ? (p.l3_fused ? 2 : 1) : 0;
+  if (int rc = p.l3_fused ? reduce_slabs(segs, b.sq_err ? 3 : 2, s, &u, assign) : reduce_slabs(segs, 1, s, nullptr, assign))
+    return rc;
+  return update ? 2 : 1;
 }
 
-template <int N1, int N2, int F1, int F3>
-static int dispatch_one(const srcnn_net* net, const float* X, const float* T, uint32_t w,
-                        uint32_t h, uint32_t batch, const float* params, float* grads,
-                        float* sq_err, float* A1, float* A2, float* D2, float* A3, float* D3,
-                        float* slab, size_t slab_bytes, hipStream_t s, bool query_only,
-                        size_t* need, const SlabUpdate* up, const LazyUpdate* lz) {
-  if (net->n1 != (uint32_t)N1 || net->n2 != (uint32_t)N2 || net->f1 != (uint32_t)F1 ||
-      net->f2 != 1 || net->f3 != (uint32_t)F3)
-    return 0;
-  return run<N1, N2, F1, F3>(X, T, w, h, batch, params, grads, sq_err, A1, A2, D2, A3, D3, slab,
-                             slab_bytes, s, query_only, need, up, lz);
+bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, StepNeed* need) {
+  return with_net(net, [&](auto n) {
+    StepPlan p;
+    if (!plan_step<decltype(n)>(w, h, batch, g_arith, &p)) return 0;
+    *need = {p.bytes, p.a1_layout};
+    return 1;
+  });
 }
 
-template <int N1, int N2, int F1, int F3>
-static int preload_one(const srcnn_net* net) {
-  if (net->n1 != (uint32_t)N1 || net->n2 != (uint32_t)N2 || net->f1 != (uint32_t)F1 ||
-      net->f2 != 1 || net->f3 != (uint32_t)F3)
-    return 0;
-  const void* k[] = {(const void*)l12_fwd_kernel<N1, N2, F1>, (const void*)l12_fwd_kernel<N1, N2, F1, true>,
-                     (const void*)l3_delta_kernel<N2, F3>, (const void*)d1_grad12_kernel<N1, N2, F1>,
-                     (const void*)slab_reduce_kernel, (const void*)l3r_delta_kernel<F3, false>,
-                     (const void*)l3r_delta_kernel<F3, true>, (const void*)d1c_grad12_kernel<9>,
-                     (const void*)l12x6_fwd_kernel<false>, (const void*)l12x6_fwd_kernel<true>,
-                     (const void*)d1x6_grad12_kernel<false>, (const void*)d1x6_grad12_kernel<true>};
-  const int rc = resolve_kernels(k, N1 == 64 && N2 == 32 && F1 == 9 ? 12 : 7);
-  return rc ? rc : 1;
+int train_fwd_bwd(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, const StepBuffers& b,
+                  hipStream_t s, const SlabUpdate* up, const LazyUpdate* lz) {
+  return with_net(net, [&](auto n) {
+    StepPlan p;
+    if (!plan_step<decltype(n)>(w, h, batch, g_arith, &p)) return 0;
+    return run<decltype(n)>(p, net, w, h, batch, b, s, up, lz);
+  });
 }
 
 int preload(const srcnn_net* net) {
-  int rc;
-  if ((rc = preload_one<64, 32, 9, 5>(net)) || (rc = preload_one<32, 16, 9, 5>(net)) ||
-      (rc = preload_one<64, 32, 9, 3>(net)) || (rc = preload_one<32, 16, 9, 3>(net)))
-    return rc;
-  return 0;
+  return with_net(net, [&](auto n) {
+    using N = decltype(n);
+    const void* k[] = {(const void*)l12_fwd_kernel<N::N1, N::N2, N::F1>, (const void*)l12_fwd_kernel<N::N1, N::N2, N::F1, true>,
+                       (const void*)l3_delta_kernel<N::N2, N::F3>, (const void*)d1_grad12_kernel<N::N1, N::N2, N::F1>,
+                       (const void*)slab_reduce_kernel, (const void*)l3r_delta_kernel<N::F3, false>,
+                       (const void*)l3r_delta_kernel<N::F3, true>, (const void*)d1c_grad12_kernel<9>,
+                       (const void*)l12x6_fwd_kernel<false>, (const void*)l12x6_fwd_kernel<true>,
+                       (const void*)d1x6_grad12_kernel<false>, (const void*)d1x6_grad12_kernel<true>};
+    const int rc = resolve_kernels(k, N::kDefault12 ? 12 : 7);
+    return rc ? rc : 1;
+  });
 }
 
 // blocked A1 (l12_fwd_kernel's store layout) -> reference HWC, for
@@ -1214,10 +1168,6 @@ __global__ void unrun_a1_kernel(const float* __restrict__ A1t, float* __restrict
   }
 }
 
-bool a1_runs(const srcnn_net* net, uint32_t w, uint32_t h) {
-  return net->f2 == 1 && x6_active((int)net->n1, (int)net->n2, (int)net->f1, w, h);
-}
-
 void note_a1_layout(const float* A1, int layout) {
   t_a1_region = A1;
   t_a1_layout = layout;
@@ -1253,24 +1203,6 @@ int train_clock(int slot, double* ghz) {
   SRCNN_HIP_TRY(hipMemcpyFromSymbol(a, HIP_SYMBOL(g_clk), sizeof(a)));
   *ghz = clock_ghz(a[slot]);
   return SRCNN_OK;
-}
-
-int train_fwd_bwd(const srcnn_net* net, const float* X, const float* T, uint32_t w, uint32_t h,
-                  uint32_t batch, const float* params, float* grads, float* sq_err, float* A1,
-                  float* A2, float* D2, float* A3, float* D3, float* slab, size_t slab_bytes,
-                  hipStream_t s, bool query_only, size_t* need, const SlabUpdate* up,
-                  const LazyUpdate* lz) {
-  int rc;
-#define SRCNN_FUSED_CASE(n1, n2, f1, f3)                                                             \
-  if ((rc = dispatch_one<n1, n2, f1, f3>(net, X, T, w, h, batch, params, grads, sq_err, A1, A2,      \
-                                         D2, A3, D3, slab, slab_bytes, s, query_only, need, up, lz)) != 0) \
-    return rc;
-  SRCNN_FUSED_CASE(64, 32, 9, 5)  // reference default (BASELINE.json configs[1])
-  SRCNN_FUSED_CASE(32, 16, 9, 5)  // example_config.json
-  SRCNN_FUSED_CASE(64, 32, 9, 3)  // the default / example nets with a 3x3 last layer
-  SRCNN_FUSED_CASE(32, 16, 9, 3)
-#undef SRCNN_FUSED_CASE
-  return 0;
 }
 
 }  // namespace fused

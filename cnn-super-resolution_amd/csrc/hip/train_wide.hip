@@ -2299,23 +2299,29 @@ struct Net {
 
 static size_t align_f(size_t n) { return (n + 63) & ~(size_t)63; }
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return SRCNN_OK;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess)
-    return fail(SRCNN_ERR_HIP, "hipFuncSetAttribute(%zu B LDS): %s", bytes, hipGetErrorString(e));
-  return SRCNN_OK;
-}
+// Everything the step decides before its first launch.  plan_step fills it
+// from the shape and the arithmetic alone: no buffer, no HIP call.
+struct WidePlan {
+  WGeom g;
+  CGeom cf, cd;  // L2 forward, delta1
+  G2Geom g2;     // wgrad2 bands; groups = the launched kernel's sample groups
+  // split-bf16 kernels: x6 wl2x6 (L2 forward), x6d wd1x6 (delta1 into D1,
+  // then gW1 apart), x6f wl1x6 (L1 forward), x6g1 wg1x6 (gW1 after wd1x6, else
+  // l1_grad_kernel), x6g wgrad2x6.  wl3l: layer 3 with the A2 image in LDS.
+  bool x6, x6d, x6f, x6g1, x6g, wl3l;
+  int qfloats;                                 // wl3's Q image
+  RunGeom rg1;                                 // layer 1's runs (wl1x6, wg1x6)
+  int GL1, GL2, G3, GD, GW1, GG1, GG2, nslab1;  // grids: L1, L2, layer 3, delta1, l1_grad, wg1x6, grad2; gW1 slabs
+  size_t lds1, lds2, lds3, ldsd, ldsg1, ldsg2;  // dynamic LDS bytes of the launched variants
+  // workspace in floats: Wf | Wd | Wx (split W2 image, wl2x6) | Wx1 (split flipped W2, wd1x6) | slab1 | slab2 | slab3 | sqs
+  size_t nWf, nWd, nWx, n1, n2, n3, nsq, bytes;
+};
 
 template <int N1, int N2, int F1, int F2, int F3>
-static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t batch,
-               const float* params, float* grads, float* sq_err, float* A1, float* D1, float* A2,
-               float* D2, float* A3, float* slab, size_t slab_bytes, hipStream_t s, bool query_only,
-               size_t* need, const fused::SlabUpdate* up) {
+static bool plan_step(uint32_t w, uint32_t h, uint32_t batch, int arith, WidePlan* out) {
   using NetT = Net<N1, N2, F1, F2, F3>;
-  WGeom g;
+  WidePlan& p = *out = {};
+  WGeom& g = p.g;
   g.w = (int)w;
   g.h = (int)h;
   g.w1 = g.w - F1 + 1;
@@ -2325,212 +2331,194 @@ static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t 
   g.w3 = g.w2 - F3 + 1;
   g.h3 = g.h2 - F3 + 1;
   g.batch = (int)batch;
-  if (g.w > kXS || g.h > kXS || g.w3 <= 0 || g.h3 <= 0) return 0;
+  if (g.w > kXS || g.h > kXS || g.w3 <= 0 || g.h3 <= 0) return false;
   const int npx1 = g.w1 * g.h1, npx2 = g.w2 * g.h2;
   // L2 forward / delta1 geometry limits (register tiles, LDS images)
-  CGeom cf{g.w1, g.h1, 0, g.w1, g.h1, g.w2, g.h2, npx2, g.batch, 0, 0, 0};
-  CGeom cd{g.w2, g.h2, F2 - 1, g.w2 + 2 * (F2 - 1), g.h2 + 2 * (F2 - 1), g.w1, g.h1, npx1, g.batch,
-           g.w, g.h, 0};
-  if ((npx2 + 31) / 32 > 2 * NetT::MT2 || (npx1 + 31) / 32 > 2 * NetT::MT4) return 0;
-  if (cf.img_w * cf.img_h > kImgMax || cd.img_w * cd.img_h > kImgMax) return 0;
+  const CGeom cf = p.cf = {g.w1, g.h1, 0, g.w1, g.h1, g.w2, g.h2, npx2, g.batch, 0, 0, 0};
+  const CGeom cd = p.cd = {g.w2, g.h2, F2 - 1, g.w2 + 2 * (F2 - 1), g.h2 + 2 * (F2 - 1), g.w1, g.h1, npx1, g.batch,
+                           g.w, g.h, 0};
+  if ((npx2 + 31) / 32 > 2 * NetT::MT2 || (npx1 + 31) / 32 > 2 * NetT::MT4) return false;
+  if (cf.img_w * cf.img_h > kImgMax || cd.img_w * cd.img_h > kImgMax) return false;
   // wgrad2 bands
-  G2Geom g2;
+  G2Geom& g2 = p.g2;
   g2.w1 = g.w1;
   g2.h1 = g.h1;
   g2.w2 = g.w2;
   g2.h2 = g.h2;
   g2.rows = std::min(8, kBandPx / g.w2);
-  if (g2.rows < 1 || (g2.rows + F2 - 1) * g.w1 > kGAPx) return 0;
+  if (g2.rows < 1 || (g2.rows + F2 - 1) * g.w1 > kGAPx) return false;
   g2.cols = g.w2;  // full-width bands
   g2.nbx = 1;
   g2.aw = g.w1;
   g2.nbands = (g.h2 + g2.rows - 1) / g2.rows;
   g2.batch = g.batch;
-  g2.groups = (int)std::min<uint32_t>(batch, 64);
-  // wl3 LDS
-  const int qfloats = std::max(npx2 * F3 * F3, 2 * 16 * 64 * 4);
-  const size_t lds3 = (size_t)(qfloats + (g.w3 + 2 * (F3 - 1)) * (g.h3 + 2 * (F3 - 1)) + 2 * npx2) * 4;
-  if (lds3 > 64 * 1024) return 0;
-  // wl3l: A2 image + Q + delta3 grid (the reduction reuses the A2 image)
-  const size_t lds3l = (size_t)(npx2 * N2 + npx2 * F3 * F3 + (g.w3 + 2 * (F3 - 1)) * (g.h3 + 2 * (F3 - 1))) * 4;
-  // the 160 KiB LDS also holds wl3l's static red_s[2][8] (64 B)
+  // the split-bf16 wgrad2 (wgrad2x6) takes fewer sample groups (one block per
+  // CU); slab2 is sized for wgrad2's, so it holds either arithmetic's
+  const int groups2 = (int)std::min<uint32_t>(batch, 64);
+  p.x6g = arith == 0 && F2 == 5 && N2 == 64 && N1 % 16 == 0 && g.w2 <= kG6MaxW2;
+  g2.groups = p.x6g ? (int)std::min<uint32_t>(batch, kG6Groups) : groups2;
+  p.GG2 = p.x6g ? g2.groups * (N1 / 16) : groups2 * (N1 / 32);
+  p.ldsg2 = p.x6g ? kG6Lds : 2 * (size_t)kGBuf * sizeof(float);
+  // layer 3.  wl3: Q + the delta3 grid + 2 A2 pixels' worth; wl3l: A2 image
+  // + Q + delta3 grid (the reduction reuses the A2 image), and the 160 KiB
+  // LDS also holds wl3l's static red_s[2][8] (64 B)
+  p.qfloats = std::max(npx2 * F3 * F3, 2 * 16 * 64 * 4);
+  const int d3grid = (g.w3 + 2 * (F3 - 1)) * (g.h3 + 2 * (F3 - 1));
+  const size_t lds3 = (size_t)(p.qfloats + d3grid + 2 * npx2) * 4;
+  if (lds3 > 64 * 1024) return false;
+  const size_t lds3l = (size_t)(npx2 * N2 + npx2 * F3 * F3 + d3grid) * 4;
   constexpr size_t kWl3lStaticLds = 2 * 8 * sizeof(float);
-  const bool wl3l = lds3l + kWl3lStaticLds <= 160 * 1024 && npx2 * N2 >= 2 * 16 * 64 * 8 &&
-                    g.w3 * g.h3 <= 512;
-  constexpr int NPD = N1 / 64;  // delta1 items per sample (64-channel parts)
-  const int GD = std::min(g.batch * NPD, 256);  // a multiple of NPD: block parity = part
-  const int G1 = GD / NPD;                      // gW1 slabs: one per block pair
-  const int G3 = (int)std::min<uint32_t>(batch, wl3l ? 256 : 512);  // all blocks resident
-  const int GC = 256;
-  const int G2 = g2.groups * (N1 / 32);
-  // workspace: Wf | Wd | Wx (split W2 image, wl2x6) | Wx1 (split flipped W2, wd1x6) | slab1 | slab2 | slab3 | sqs
-  const size_t nWf = align_f(NetT::W2), nWd = align_f(NetT::W2), nWx = align_f((size_t)NetT::W2 * 3 / 2);
-  // the split-bf16 L2 forward (wl2x6): two split chunk images in LDS
+  p.wl3l = lds3l + kWl3lStaticLds <= 160 * 1024 && npx2 * N2 >= 2 * 16 * 64 * 8 && g.w3 * g.h3 <= 512;
+  p.lds3 = p.wl3l ? lds3l : lds3;
+  p.G3 = (int)std::min<uint32_t>(batch, p.wl3l ? 256 : 512);  // all blocks resident
+  // L1 forward: split-bf16 wl1x6, else wl1_fwd
+  p.rg1 = run_geom(g.w1, g.h1);
+  p.x6f = arith == 0 && wl1x6_fits(g.w, g.h, N1, F1);
+  p.GL1 = (int)std::min<uint32_t>(batch, 1024);
+  p.lds1 = p.x6f ? W1x6Lds(g.w, g.h, p.rg1).bytes : 0;
+  // L2 forward: split-bf16 wl2x6 (two split chunk images in LDS), else conv_mfma
   const size_t lds6 = 2 * (size_t)cf.img_h * w6_pitch(cf.img_w, cf.out_w) * sizeof(float);
-  const bool x6 = g_arith == 0 && N2 == 64 && N1 % 16 == 0 && cf.img_w * cf.img_h <= kW6ImgMax &&
-                  lds6 <= 160 * 1024;
-  // the split-bf16 delta1 (wd1x6 into D1, then gW1 by l1_grad_kernel over GW1 slabs)
+  p.x6 = arith == 0 && N2 == 64 && N1 % 16 == 0 && cf.img_w * cf.img_h <= kW6ImgMax && lds6 <= 160 * 1024;
+  p.GL2 = std::min(p.x6 ? g.batch : g.batch * (N2 / 64), 256);
+  p.lds2 = p.x6 ? lds6 : 2 * ((size_t)cf.img_w * cf.img_h * kPS + kImgSlack) * sizeof(float);
+  // delta1: split-bf16 wd1x6 into D1, then gW1 by wg1x6 (two blocks per CU)
+  // or l1_grad_kernel (4 per CU) over their own slabs; else d1g16 does both
   const size_t lds_d6 = (size_t)cd.img_h * w6_pitch(cd.img_w, cd.out_w) * sizeof(float);
-  const bool x6d = g_arith == 0 && N1 % 64 == 0 && N2 % 16 == 0 && cd.img_w * cd.img_h <= kWD6ImgMax &&
-                   (npx1 + 31) / 32 <= 2 * NetT::MT4 && D1 != nullptr && lds_d6 <= 160 * 1024;
-  const int GW1 = (int)std::min<uint32_t>(batch, 1024);  // (4 blocks of l1_grad_kernel per CU)
-  // the split-bf16 L1 forward (wl1x6) and gW1 (wg1x6, after wd1x6: two blocks per CU)
-  const bool x6f = g_arith == 0 && wl1x6_fits(g.w, g.h, N1, F1);
-  const bool x6g1 = g_arith == 0 && wg1x6_fits(g.w, g.h, N1, F1);
-  const int GG1 = (int)std::min<uint32_t>(batch, 512);
-  const size_t n1 = align_f((size_t)std::max(G1, GW1) * NetT::P1), n2 = align_f((size_t)g2.groups * NetT::P2);
-  // the split-bf16 wgrad2 (wgrad2x6): fewer sample groups (one block per CU), so the slab fits
-  const bool x6g = g_arith == 0 && F2 == 5 && N2 == 64 && N1 % 16 == 0 && g.w2 <= kG6MaxW2;
-  if (x6g) g2.groups = (int)std::min<uint32_t>(batch, kG6Groups);
-  const size_t n3 = align_f((size_t)G3 * NetT::P3), nsq = align_f(G3);
-  const size_t bytes = (nWf + nWd + 2 * nWx + n1 + n2 + n3 + nsq) * sizeof(float);
-  if (query_only) {
-    *need = bytes;
-    return 1;
-  }
-  if (slab_bytes < bytes)
-    return fail(SRCNN_ERR_WORKSPACE, "wide train step: workspace %zu B < %zu B", slab_bytes, bytes);
-  float* Wf = slab;
-  float* Wd = Wf + nWf;
-  uint16_t* Wx = reinterpret_cast<uint16_t*>(Wd + nWd);
-  uint16_t* Wx1 = reinterpret_cast<uint16_t*>(Wd + nWd + nWx);
-  float* slab1 = Wd + nWd + 2 * nWx;
-  float* slab2 = slab1 + n1;
-  float* slab3 = slab2 + n2;
-  float* sqs = slab3 + n3;
-  const float* W1 = params;
-  const float* B1 = W1 + NetT::W1;
-  const float* W2 = B1 + N1;
-  const float* B2 = W2 + NetT::W2;
-  const float* W3 = B2 + N2;
-  const float* B3 = W3 + NetT::W3;
+  p.x6d = arith == 0 && N1 % 64 == 0 && N2 % 16 == 0 && cd.img_w * cd.img_h <= kWD6ImgMax &&
+          (npx1 + 31) / 32 <= 2 * NetT::MT4 && lds_d6 <= 160 * 1024;
+  p.x6g1 = arith == 0 && wg1x6_fits(g.w, g.h, N1, F1);
+  constexpr int NPD = N1 / 64;                // delta1 items per sample (64-channel parts)
+  p.GD = std::min(g.batch * NPD, 256);        // a multiple of NPD: block parity = part
+  const int G1 = p.GD / NPD;                  // d1g16's gW1 slabs: one per block pair
+  p.GW1 = (int)std::min<uint32_t>(batch, 1024);
+  p.GG1 = (int)std::min<uint32_t>(batch, 512);
+  p.nslab1 = p.x6d ? (p.x6g1 ? p.GG1 : p.GW1) : G1;
+  // d1g16: + the slot -> pixel table, tile masks, tile order
+  p.ldsd = p.x6d ? lds_d6
+                 : (2 * ((size_t)cd.img_w * cd.img_h * kPS + kImgSlack) + 2 * kXBuf + kD16Slots + 4 * kD16MT) * sizeof(float);
+  p.ldsg1 = p.x6d && p.x6g1 ? G1x6Lds(g.w, g.h, p.rg1).bytes : 0;
+  p.nWf = p.nWd = align_f(NetT::W2);
+  p.nWx = align_f((size_t)NetT::W2 * 3 / 2);
+  p.n1 = align_f((size_t)std::max(G1, p.GW1) * NetT::P1);
+  p.n2 = align_f((size_t)groups2 * NetT::P2);
+  p.n3 = align_f((size_t)p.G3 * NetT::P3);
+  p.nsq = align_f(p.G3);
+  p.bytes = (p.nWf + p.nWd + 2 * p.nWx + p.n1 + p.n2 + p.n3 + p.nsq) * sizeof(float);
+  return true;
+}
+
+// Carves the workspace and launches in order; every decision comes from the
+// plan.  Each kernel has one profile scope, under either arithmetic.
+template <int N1, int N2, int F1, int F2, int F3>
+static int run(const WidePlan& p, const srcnn_net* net, const StepBuffers& b, hipStream_t s,
+               const fused::SlabUpdate* up) {
+  using NetT = Net<N1, N2, F1, F2, F3>;
+  if (b.slab_bytes < p.bytes)
+    return fail(SRCNN_ERR_WORKSPACE, "wide train step: workspace %zu B < %zu B", b.slab_bytes, p.bytes);
+  float* Wf = b.slab;
+  float* Wd = Wf + p.nWf;
+  uint16_t* Wx = reinterpret_cast<uint16_t*>(Wd + p.nWd);
+  uint16_t* Wx1 = reinterpret_cast<uint16_t*>(Wd + p.nWd + p.nWx);
+  float* slab1 = Wd + p.nWd + 2 * p.nWx;
+  float* slab2 = slab1 + p.n1;
+  float* slab3 = slab2 + p.n2;
+  float* sqs = slab3 + p.n3;
+  const auto P = split_params(b.params, net);
+  const float *X = b.X, *T = b.T;
+  float *A1 = b.A1, *D1 = b.D1, *A2 = b.A2, *D2 = b.D2, *A3 = b.A3;
+  const WGeom& g = p.g;
+  const dim3 blk(256);
   {
     SRCNN_PROFILE("wide_prepack_w2", s);
-    const int tot = 2 * NetT::W2;
-    hipLaunchKernelGGL((prepack_w2_kernel<N1, N2, F2, true>), dim3((tot + 255) / 256), dim3(256), 0, s,
-                       W2, Wf, Wd);
-    SRCNN_LAUNCH_TRY();
-    if (x6) {
-      const int totx = (N2 / 32) * (N1 / 16) * F2 * F2 * 512;
-      hipLaunchKernelGGL((wprep_w2x6_kernel<N1, N2, F2>), dim3((totx + 255) / 256), dim3(256), 0, s, W2, Wx);
-      SRCNN_LAUNCH_TRY();
-    }
-    if (x6d) {
-      const int totx = (N1 / 32) * (N2 / 16) * F2 * F2 * 512;
-      hipLaunchKernelGGL((wprep_d1x6_kernel<N1, N2, F2>), dim3((totx + 255) / 256), dim3(256), 0, s, W2, Wx1);
-      SRCNN_LAUNCH_TRY();
-    }
+    auto blocks = [](int tot) { return dim3((tot + 255) / 256); };
+    if (int rc = launch(prepack_w2_kernel<N1, N2, F2, true>, blocks(2 * NetT::W2), blk, 0, s, P.W2, Wf, Wd)) return rc;
+    if (p.x6)
+      if (int rc = launch(wprep_w2x6_kernel<N1, N2, F2>, blocks((N2 / 32) * (N1 / 16) * F2 * F2 * 512), blk, 0, s, P.W2, Wx))
+        return rc;
+    if (p.x6d)
+      if (int rc = launch(wprep_d1x6_kernel<N1, N2, F2>, blocks((N1 / 32) * (N2 / 16) * F2 * F2 * 512), blk, 0, s, P.W2, Wx1))
+        return rc;
   }
   {
     SRCNN_PROFILE("wide_l1_fwd", s);
-    if (x6f) {
-      kernels_note("wl1x6_fwd");
-      const RunGeom rg1 = run_geom(g.w1, g.h1);
-      if (int rc = set_lds(wl1x6_fwd_kernel, W1x6Lds(g.w, g.h, rg1).bytes)) return rc;
-      hipLaunchKernelGGL(wl1x6_fwd_kernel, dim3(std::min<uint32_t>(batch, 1024)), dim3(256),
-                         W1x6Lds(g.w, g.h, rg1).bytes, s, X, W1, B1, A1, g, rg1);
-    } else {
-      kernels_note("wide_l1_fwd");
-      hipLaunchKernelGGL((wl1_fwd_kernel<N1, F1>), dim3(std::min<uint32_t>(batch, 1024)), dim3(256),
-                         0, s, X, W1, B1, A1, g);
-    }
-    SRCNN_LAUNCH_TRY();
+    kernels_note(p.x6f ? "wl1x6_fwd" : "wide_l1_fwd");
+    if (int rc = p.x6f ? launch(wl1x6_fwd_kernel, dim3(p.GL1), blk, p.lds1, s, X, P.W1, P.B1, A1, g, p.rg1)
+                       : launch(wl1_fwd_kernel<N1, F1>, dim3(p.GL1), blk, 0, s, X, P.W1, P.B1, A1, g))
+      return rc;
   }
   {
     SRCNN_PROFILE("wide_l2_fwd", s);
-    kernels_note(x6 ? "wl2x6_fwd" : "wide_l2_fwd");
-    if (x6) {
-      if (int rc = set_lds(wl2x6_fwd_kernel<N1, N2, F2, NetT::MT2>, lds6)) return rc;
-      hipLaunchKernelGGL((wl2x6_fwd_kernel<N1, N2, F2, NetT::MT2>), dim3(std::min(g.batch, GC)), dim3(256),
-                         lds6, s, A1, Wx, B2, A2, cf);
-      SRCNN_LAUNCH_TRY();
-    }
-  }
-  if (!x6) {
-    SRCNN_PROFILE("wide_l2_fwd", s);
-    const size_t lds = 2 * ((size_t)cf.img_w * cf.img_h * kPS + kImgSlack) * sizeof(float);
-    if (int rc = set_lds(conv_mfma_kernel<N1, N2, F2, NetT::MT2, false>, lds)) return rc;
-    const int items = g.batch * (N2 / 64);
-    hipLaunchKernelGGL((conv_mfma_kernel<N1, N2, F2, NetT::MT2, false>), dim3(std::min(items, GC)),
-                       dim3(256), lds, s, A1, Wf, B2, (const float*)nullptr, A2, cf);
-    SRCNN_LAUNCH_TRY();
+    kernels_note(p.x6 ? "wl2x6_fwd" : "wide_l2_fwd");
+    if (int rc = p.x6 ? launch(wl2x6_fwd_kernel<N1, N2, F2, NetT::MT2>, dim3(p.GL2), blk, p.lds2, s, A1, Wx, P.B2, A2, p.cf)
+                      : launch(conv_mfma_kernel<N1, N2, F2, NetT::MT2, false>, dim3(p.GL2), blk, p.lds2, s, A1, Wf, P.B2,
+                               (const float*)nullptr, A2, p.cf))
+      return rc;
   }
   {
     SRCNN_PROFILE("wide_l3_delta", s);
-    if (wl3l) {
-      if (int rc = set_lds(wl3l_kernel<N2, F3>, lds3l)) return rc;
-      hipLaunchKernelGGL((wl3l_kernel<N2, F3>), dim3(G3), dim3(512), lds3l, s, A2, T, W3, B3, D2, slab3, sqs,
-                         A3, g);
-    } else {
-      if (int rc = set_lds(wl3_kernel<N2, F3>, lds3)) return rc;
-      hipLaunchKernelGGL((wl3_kernel<N2, F3>), dim3(G3), dim3(256), lds3, s, A2, T, W3, B3, D2,
-                         slab3, sqs, A3, g, qfloats);
-    }
-    SRCNN_LAUNCH_TRY();
+    if (int rc = p.wl3l ? launch(wl3l_kernel<N2, F3>, dim3(p.G3), dim3(512), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, g)
+                        : launch(wl3_kernel<N2, F3>, dim3(p.G3), blk, p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, g,
+                                 p.qfloats))
+      return rc;
   }
   {
-    SRCNN_PROFILE(x6d ? "wide_delta1" : "wide_delta1_grad1", s);
-    kernels_note(x6d ? "wd1x6" : "d1g16");
-    if (x6d) {
-      if (int rc = set_lds(wd1x6_kernel<N2, N1, F2, NetT::MT4>, lds_d6)) return rc;
-      hipLaunchKernelGGL((wd1x6_kernel<N2, N1, F2, NetT::MT4>), dim3(GD), dim3(256), lds_d6, s, D2, Wx1, D1, cd);
-      SRCNN_LAUNCH_TRY();
-    }
+    SRCNN_PROFILE(p.x6d ? "wide_delta1" : "wide_delta1_grad1", s);
+    kernels_note(p.x6d ? "wd1x6" : "d1g16");
+    if (int rc = p.x6d ? launch(wd1x6_kernel<N2, N1, F2, NetT::MT4>, dim3(p.GD), blk, p.ldsd, s, D2, Wx1, D1, p.cd)
+                       : launch(d1g16_kernel<N2, N1, F2, F1>, dim3(p.GD), blk, p.ldsd, s, D2, Wd, A1, X, slab1, p.cd))
+      return rc;
   }
-  if (x6d) {
+  if (p.x6d) {
     SRCNN_PROFILE("wide_grad1", s);
-    if (x6g1) {
+    if (p.x6g1) {
       kernels_note("wg1x6");
-      const RunGeom rg1 = run_geom(g.w1, g.h1);
-      const size_t lds = G1x6Lds(g.w, g.h, rg1).bytes;
-      if (int rc = set_lds(wg1x6_kernel, lds)) return rc;
-      hipLaunchKernelGGL(wg1x6_kernel, dim3(GG1), dim3(256), lds, s, X, D1, A1, slab1, g, rg1);
-      SRCNN_LAUNCH_TRY();
-    } else {
-      if (int rc = fast::l1_grad_slabs(X, D1, A1, slab1, N1, F1, g.w, g.h, g.batch, GW1, s); rc != 1)
-        return rc ? rc : fail(SRCNN_ERR_INVALID, "wide step: no layer-1 gradient kernel for n1 %d f1 %d", N1, F1);
+      if (int rc = launch(wg1x6_kernel, dim3(p.GG1), blk, p.ldsg1, s, X, D1, A1, slab1, g, p.rg1)) return rc;
+    } else if (int rc = fast::l1_grad_slabs(X, D1, A1, slab1, N1, F1, g.w, g.h, g.batch, p.GW1, s); rc != 1) {
+      return rc ? rc : fail(SRCNN_ERR_INVALID, "wide step: no layer-1 gradient kernel for n1 %d f1 %d", N1, F1);
     }
-  }
-  if (!x6d) {
-    SRCNN_PROFILE("wide_delta1_grad1", s);
-    const size_t lds = (2 * ((size_t)cd.img_w * cd.img_h * kPS + kImgSlack) + 2 * kXBuf + kD16Slots +
-                        4 * kD16MT) * sizeof(float);  // + the slot -> pixel table, tile masks, tile order
-    if (int rc = set_lds(d1g16_kernel<N2, N1, F2, F1>, lds)) return rc;
-    hipLaunchKernelGGL((d1g16_kernel<N2, N1, F2, F1>), dim3(GD), dim3(256), lds, s, D2, Wd, A1, X, slab1, cd);
-    SRCNN_LAUNCH_TRY();
   }
   {
     SRCNN_PROFILE("wide_grad2", s);
-    kernels_note(x6g ? "wgrad2x6" : "wgrad2");
-    if (x6g) {
-      if (int rc = set_lds(wgrad2x6_kernel<N1, N2, F2>, kG6Lds)) return rc;
-      hipLaunchKernelGGL((wgrad2x6_kernel<N1, N2, F2>), dim3(g2.groups * (N1 / 16)), dim3(512), kG6Lds, s, A1,
-                         D2, slab2, g2);
-      SRCNN_LAUNCH_TRY();
-    }
+    kernels_note(p.x6g ? "wgrad2x6" : "wgrad2");
+    if (int rc = p.x6g ? launch(wgrad2x6_kernel<N1, N2, F2>, dim3(p.GG2), dim3(512), p.ldsg2, s, A1, D2, slab2, p.g2)
+                       : launch(wgrad2_kernel<N1, N2, F2>, dim3(p.GG2), dim3(512), p.ldsg2, s, A1, D2, slab2, p.g2))
+      return rc;
   }
-  if (!x6g) {
-    SRCNN_PROFILE("wide_grad2", s);
-    const size_t lds = 2 * (size_t)kGBuf * sizeof(float);
-    if (int rc = set_lds(wgrad2_kernel<N1, N2, F2>, lds)) return rc;
-    hipLaunchKernelGGL((wgrad2_kernel<N1, N2, F2>), dim3(G2), dim3(512), lds, s, A1, D2, slab2, g2);
-    SRCNN_LAUNCH_TRY();
+  SRCNN_PROFILE("slab_reduce", s);
+  const fused::SlabSeg segs[4] = {{slab1, b.grads, p.nslab1, NetT::P1},
+                                  {slab2, b.grads + NetT::P1, p.g2.groups, NetT::P2},
+                                  {slab3, b.grads + NetT::P1 + NetT::P2, p.G3, NetT::P3},
+                                  {sqs, b.sq_err, p.G3, 1}};
+  // with `up` (srcnn_train_step), segments 0-2 are every parameter
+  fused::SlabUpdate u{};
+  if (up) {
+    u = *up;
+    u.nseg = 3;
   }
-  {
-    SRCNN_PROFILE("slab_reduce", s);
-    const fused::SlabSeg segs[4] = {{slab1, grads, x6d ? (x6g1 ? GG1 : GW1) : G1, NetT::P1},
-                                    {slab2, grads + NetT::P1, g2.groups, NetT::P2},
-                                    {slab3, grads + NetT::P1 + NetT::P2, G3, NetT::P3},
-                                    {sqs, sq_err, G3, 1}};
-    // with `up` (srcnn_train_step), segments 0-2 are every parameter
-    fused::SlabUpdate u{};
-    if (up) {
-      u = *up;
-      u.nseg = 3;
-    }
-    if (int rc = fused::reduce_slabs(segs, sq_err ? 4 : 3, s, &u)) return rc;
-  }
+  if (int rc = fused::reduce_slabs(segs, b.sq_err ? 4 : 3, s, &u)) return rc;
   return up ? 2 : 1;
+}
+
+// the one instantiated net: plan, run and preload all ask here
+using WideNet = Net<128, 64, 9, 5, 5>;
+static const auto plan_wide = plan_step<128, 64, 9, 5, 5>;
+static const auto run_wide = run<128, 64, 9, 5, 5>;
+static bool is_wide_net(const srcnn_net* net) {
+  return net->n1 == 128 && net->n2 == 64 && net->f1 == 9 && net->f2 == 5 && net->f3 == 5;
+}
+
+bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, StepNeed* need) {
+  WidePlan p;
+  if (!is_wide_net(net) || !plan_wide(w, h, batch, g_arith, &p)) return false;
+  *need = {p.bytes, fused::kA1Hwc};
+  return true;
+}
+
+int train_fwd_bwd(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, const StepBuffers& b,
+                  hipStream_t s, const fused::SlabUpdate* up) {
+  WidePlan p;
+  if (!is_wide_net(net) || !plan_wide(w, h, batch, g_arith, &p)) return 0;
+  return run_wide(p, net, b, s, up);
 }
 
 // ---------------------------------------------------------------------------
@@ -2542,7 +2530,6 @@ static int run(const float* X, const float* T, uint32_t w, uint32_t h, uint32_t 
 // 0 = shape not served here, < 0 = error.
 // ---------------------------------------------------------------------------
 namespace {
-using WideNet = Net<128, 64, 9, 5, 5>;
 constexpr int kWN1 = 128, kWN2 = 64, kWF = 5;
 
 // W2 operand images of the op-level calls: ONE device buffer per device
@@ -2623,15 +2610,11 @@ int op_conv_fwd(const float* in, float* out, const float* W, const float* B, uin
   if (w2i.rc()) return w2i.rc();
   float* img = w2i.img();
   const size_t lds = 2 * ((size_t)cf.img_w * cf.img_h * kPS + kImgSlack) * sizeof(float);
-  if (int rc = set_lds(conv_mfma_kernel<kWN1, kWN2, kWF, WideNet::MT2, false>, lds)) return rc;
-  {
-    SRCNN_PROFILE("conv_fwd_wide_mfma", s);
-    const int items = (int)batch * (kWN2 / 64) * conv_windows(cf);
-    hipLaunchKernelGGL((conv_mfma_kernel<kWN1, kWN2, kWF, WideNet::MT2, false>),
-                       dim3(std::min(items, 256)), dim3(256), lds, s, in, img, B,
-                       (const float*)nullptr, out, cf);
-    SRCNN_LAUNCH_TRY();
-  }
+  SRCNN_PROFILE("conv_fwd_wide_mfma", s);
+  const int items = (int)batch * (kWN2 / 64) * conv_windows(cf);
+  if (int rc = launch(conv_mfma_kernel<kWN1, kWN2, kWF, WideNet::MT2, false>, dim3(std::min(items, 256)), dim3(256),
+                      lds, s, in, img, B, (const float*)nullptr, out, cf))
+    return rc;
   return 1;
 }
 
@@ -2653,15 +2636,11 @@ int op_conv_delta(const float* d_next, const float* y_curr, float* d_curr, const
   if (w2i.rc()) return w2i.rc();
   float* img = w2i.img();
   const size_t lds = 2 * ((size_t)cd.img_w * cd.img_h * kPS + kImgSlack) * sizeof(float);
-  if (int rc = set_lds(conv_mfma_kernel<kWN2, kWN1, kWF, WideNet::MT4, true>, lds)) return rc;
-  {
-    SRCNN_PROFILE("conv_delta_wide_mfma", s);
-    const int items = (int)batch * (kWN1 / 64) * conv_windows(cd);
-    hipLaunchKernelGGL((conv_mfma_kernel<kWN2, kWN1, kWF, WideNet::MT4, true>),
-                       dim3(std::min(items, 256)), dim3(256), lds, s, d_next,
-                       img + align_f(WideNet::W2), (const float*)nullptr, y_curr, d_curr, cd);
-    SRCNN_LAUNCH_TRY();
-  }
+  SRCNN_PROFILE("conv_delta_wide_mfma", s);
+  const int items = (int)batch * (kWN1 / 64) * conv_windows(cd);
+  if (int rc = launch(conv_mfma_kernel<kWN2, kWN1, kWF, WideNet::MT4, true>, dim3(std::min(items, 256)), dim3(256),
+                      lds, s, d_next, img + align_f(WideNet::W2), (const float*)nullptr, y_curr, d_curr, cd))
+    return rc;
   return 1;
 }
 
@@ -2707,10 +2686,9 @@ int op_conv_grad_acc(const float* in, const float* d, float* gW, float* gB, uint
   {
     SRCNN_PROFILE("grad_wide_mfma", s);
     const size_t lds = 2 * (size_t)kGBuf * sizeof(float);
-    if (int rc = set_lds(wgrad2_kernel<kWN1, kWN2, kWF>, lds)) return rc;
-    hipLaunchKernelGGL((wgrad2_kernel<kWN1, kWN2, kWF>), dim3(g2.groups * (kWN1 / 32)), dim3(512), lds,
-                       s, in, d, slab2, g2);
-    SRCNN_LAUNCH_TRY();
+    if (int rc = launch(wgrad2_kernel<kWN1, kWN2, kWF>, dim3(g2.groups * (kWN1 / 32)), dim3(512), lds, s, in, d,
+                        slab2, g2))
+      return rc;
   }
   {
     SRCNN_PROFILE("slab_reduce", s);
@@ -2723,7 +2701,7 @@ int op_conv_grad_acc(const float* in, const float* d, float* gW, float* gB, uint
 }
 
 int preload(const srcnn_net* net) {
-  if (!(net->n1 == 128 && net->n2 == 64 && net->f1 == 9 && net->f2 == 5 && net->f3 == 5)) return 0;
+  if (!is_wide_net(net)) return 0;
   using NetT = WideNet;
   // the training step's kernels (and the op-level delta1 / forward ones)
   const void* k[] = {(const void*)prepack_w2_kernel<128, 64, 5, true>, (const void*)wl1_fwd_kernel<128, 9>,
@@ -2738,16 +2716,6 @@ int preload(const srcnn_net* net) {
                      (const void*)wg1x6_kernel};
   int rc = resolve_kernels(k, 16);
   return rc ? rc : 1;
-}
-
-int train_fwd_bwd(const srcnn_net* net, const float* X, const float* T, uint32_t w, uint32_t h,
-                  uint32_t batch, const float* params, float* grads, float* sq_err, float* A1,
-                  float* D1, float* A2, float* D2, float* A3, float* slab, size_t slab_bytes,
-                  hipStream_t s, bool query_only, size_t* need, const fused::SlabUpdate* up) {
-  if (net->n1 == 128 && net->n2 == 64 && net->f1 == 9 && net->f2 == 5 && net->f3 == 5)
-    return run<128, 64, 9, 5, 5>(X, T, w, h, batch, params, grads, sq_err, A1, D1, A2, D2, A3, slab,
-                                 slab_bytes, s, query_only, need, up);
-  return 0;
 }
 
 }  // namespace wide
