@@ -14,7 +14,9 @@
 //                  (register r of half h = slot crow(r, h)), the layout of
 //                  l12x6's transposed A1 loads, so relu'(A1) is elementwise
 //   gW2[c][n] += sum_p A1[p][c] delta2[p][n]         K = slots: A = A1^T as
-//                  loaded, B = delta2^T through a per-wave LDS transpose
+//                  loaded, B = delta2^T through a per-wave LDS transpose (of
+//                  the fp32 values, split again; kTr: of delta1's split parts,
+//                  a bf16 image read back with transposed reads, d6tr.hpp)
 //   gW1[t][c] += sum_p X[p + off(t)] delta1[p][c]    written as gW1^T: M =
 //                  channels, N = taps (3 tiles: 81 taps, the ones column of
 //                  gB1, zeros), K = slots; A = delta1 as it stands, B = X
@@ -22,7 +24,8 @@
 //                  4m + 2 + h, each 4 consecutive X values under any tap --
 //                  one ds_read2_b32 per run and part from part-interleaved
 //                  pair images (row runs: R; column runs: T, column-major)
-//   gB2[n] += sum_p delta2[p][n]                     VALU over delta2^T
+//   gB2[n] += sum_p delta2[p][n]                     VALU over delta2^T (kTr:
+//                  per lane over the rows, crossed over lanes in the epilogue)
 // Each wave accumulates over its chunks; at the end the four waves' sums are
 // added in wave order through LDS and the block writes one slab (summed by
 // slab_reduce in block order).  (One slab per wave was 4x the slab traffic:
@@ -49,6 +52,7 @@ struct D6Lds {
   // columns per part, row stride gs (dwords), gh rows; one buffer d3buf dwords
   int gw, gs, gh, d3buf;
   int w2, xb, sc, slots, runs, cst, w3i, d3tab, d3img, bytes;  // byte offsets
+  int tr;  // kD3: 1 = delta2 part images in the sc region (d6tr.hpp), 0 = the fp32 transpose scratch
   __host__ __device__ D6Lds(int w, int h, const RunGeom& rg, bool d3 = false) {
     st = 4 * rg.cr + 9;
     if (st < h + 1) st = h + 1;
@@ -65,31 +69,41 @@ struct D6Lds {
     xb = kD6W2 * 2;
     sc = xb + 2 * xbuf * 4;
     sc = (sc + 15) & ~15;
-    slots = sc + 4 * kD6Sc * 4;
-    runs = slots + rg.nch * 32 * 4;
-    cst = runs + rg.nch * 8 * 4;
-    bytes = cst + 32 * 4;
     gw = gs = gh = d3buf = 0;
-    w3i = d3tab = d3img = bytes;
-    if (d3) {
-      // slot (py, px) reads delta3 at image row py + 5 - dy, column px + 7 -
-      // dx (pairs of columns, d3taps.hpp); the padded row stride puts a
-      // chunk's 32 slots at one fixed offset on 32 banks (as l12x6's X
-      // image), unpadded where that does not fit
+    // slot (py, px) reads delta3 at image row py + 5 - dy, column px + 7 - dx
+    // (pairs of columns, d3taps.hpp); the padded row stride puts a chunk's 32
+    // slots at one fixed offset on 32 banks (as l12x6's X image).
+    // kD3 takes, in this order: the waves' delta2 part images (d6tr.hpp, tr)
+    // with padded delta3 rows; the fp32 transpose scratch (1.5 KB less per
+    // wave) with padded rows; the images with unpadded rows; the scratch with
+    // unpadded rows.  The scratch forms are the layouts this kernel had before
+    // the images, and padded rows come before the images: every shape fits
+    // exactly where it did, and none loses the padded rows it had
+    // (33x33: 151.8 KB with images and padded rows; unpadded rows' reads were
+    // 11 of d1x6's 25 conflict points)
+    const int ntry = d3 ? 4 : 1;
+    for (int k = 0; k < ntry; k++) {
+      tr = d3 && !(k & 1);
+      const bool pad = k < 2;
+      slots = sc + (tr ? d6tr_wave_off(4) : 4 * kD6Sc * 4);
+      runs = slots + rg.nch * 32 * 4;
+      cst = runs + rg.nch * 8 * 4;
+      bytes = cst + 32 * 4;
+      w3i = d3tab = d3img = bytes;
+      if (!d3) break;
       gw = rg.ow + 8;
       gh = rg.oh + 5;
       const int a4 = (4 * rg.a) % 32;
-      gs = 3 * gw + ((a4 - 3 * gw) % 32 + 32) % 32;
-      for (int k = 0; k < 2; k++) {
-        d3buf = gh * gs;
-        w3i = (cst + 32 * 4 + 15) & ~15;
-        d3tab = w3i + kD6W3 * 2;
-        d3img = d3tab + rg.nch * 32 * 4;
-        bytes = d3img + 3 * d3buf * 4 + 16;  // (+ the zeroing's last 16-B store)
-        if (bytes <= 160 * 1024) break;  // (33x33: 154.9 KB padded; at 150 KB it fell back to unpadded
-                                         // rows, whose reads were 11 of d1x6's 25 conflict points)
-        gs = 3 * gw;
-      }
+      gs = pad ? 3 * gw + ((a4 - 3 * gw) % 32 + 32) % 32 : 3 * gw;
+      d3buf = gh * gs;
+      w3i = (cst + 32 * 4 + 15) & ~15;
+      // (with the part images the slot's delta3 offset shares the slot
+      // table's dword, d6_slot_pack: a table of its own is 2.5 KB at 33x33,
+      // which the images need)
+      d3tab = tr ? slots : w3i + kD6W3 * 2;
+      d3img = tr ? w3i + kD6W3 * 2 : d3tab + rg.nch * 32 * 4;
+      bytes = d3img + 3 * d3buf * 4 + 16;  // (+ the zeroing's last 16-B store)
+      if (bytes <= 160 * 1024) break;
     }
     // the final reduction's scratch and the slab staging after it
     const int red_bytes = 4 * 4 * 16 * 64 * 4 + (81 * 64 + 64 + 64 * 32 + 32) * 4;
@@ -154,7 +168,15 @@ __device__ __forceinline__ void d6_split(const float (&v)[8], bf16x8 (&o)[3]) { 
 // after delta3 in the D2 region (M2: bit n = A2[pixel][n] > 0; the A2 rows
 // themselves, 328 MB per 4096-tile step, were read here for that one bit per
 // value).  12 MFMAs per item instead of delta2's HBM round trip (328 MB more).
-template <bool kD3>
+//
+// kTr (kD3 with D6Lds::tr): gW2's delta2 operand db holds the very parts of
+// delta1's operand da, only on other lanes, so da's parts go through a
+// per-wave bf16 image [slot][part][n] (d6tr.hpp: one ds_write2_b64 per part
+// and k-step) and come back as db through transposed reads
+// (ds_read_b64_tr_b16, two per part and k-step) instead of delta2's fp32
+// transpose and a second split; gB2 sums delta2 per lane in the row layout
+// and crosses lanes once, after the loop.  Without kTr the fp32 scratch form.
+template <bool kD3, bool kTr = false>
 __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __restrict__ X,
                                                               const float* __restrict__ A1T,
                                                               const float* __restrict__ D2,
@@ -167,6 +189,7 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   constexpr int N1 = 64, N2 = 32, F1 = 9, K1 = F1 * F1;
   constexpr int NW1 = K1 * N1, NW2 = N1 * N2, P12 = NW1 + N1 + NW2 + N2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  static_assert(kD3 || !kTr, "the part images belong to the delta3 form");
   const D6Lds L(g.W, g.H, rg, kD3);
   char* const base = reinterpret_cast<char*>(smem);
   __bf16* const w2i = reinterpret_cast<__bf16*>(base + L.w2);
@@ -193,12 +216,16 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   if ((int)blockIdx.x < g.batch) xload(blockIdx.x);
 
   // ---- per-block tables and images ----
-  for (int i = threadIdx.x; i < nch * 32; i += 256) slots[i] = slot_pixel(rg, i >> 5, i & 31);
+  if constexpr (!kTr)
+    for (int i = threadIdx.x; i < nch * 32; i += 256) slots[i] = slot_pixel(rg, i >> 5, i & 31);
   for (int k = threadIdx.x; k < nch * 8; k += 256) {
     int iy, ix;
     bool col;
     run_origin(rg, k < rg.nrun ? k : 0, iy, ix, col);
-    runs[k] = col ? ~(L.rdw + 3 * ((ix - x0col) * L.st + iy)) : 3 * (iy * L.rs + ix);
+    // (a chunk's codes by lane half: k-step m of half h takes runs 4m + h
+    // and 4m + 2 + h, the four of a half one 16-B read)
+    runs[(k & ~7) + 4 * (k & 1) + 2 * ((k >> 2) & 1) + ((k >> 1) & 1)] =
+        col ? ~(L.rdw + 3 * ((ix - x0col) * L.st + iy)) : 3 * (iy * L.rs + ix);
   }
   // T rows past the tile (and the pair partner of the last row), and the R
   // rows' pad columns, stay zero (16-B stores: the region ends on the 16-B
@@ -291,11 +318,12 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       for (int q = 0; q < 3; q++) w3i[((s_ * 3 + q) * 64 + L_) * 8 + j] = p[q];
     }
     // slot -> its delta3 image offset py gs + px (dummy slots: pixel (0, 0))
+    // (kTr: in one dword with the slot's pixel, d6_slot_pack)
     int* const d3tab = reinterpret_cast<int*>(base + L.d3tab);
     for (int i = threadIdx.x; i < nch * 32; i += 256) {
       int iy, ix;
       slot_coord(rg, i >> 5, i & 31, iy, ix);
-      d3tab[i] = iy * L.gs + ix;
+      d3tab[i] = kTr ? d6_slot_pack(slot_pixel(rg, i >> 5, i & 31), iy * L.gs + ix) : iy * L.gs + ix;
     }
     for (int i = threadIdx.x; i < (3 * L.d3buf + 3) / 4; i += 256)  // borders stay zero
       reinterpret_cast<uint4*>(d3u)[i] = uint4{0u, 0u, 0u, 0u};
@@ -307,15 +335,21 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
 
   // gW1 operand offsets of this lane's tap 32u + li (3 dwords per pair
   // position); tile 2's lanes past tap 80 read the constant images
+  // (byte offsets, as the run bases of an item are: an address is one select
+  // and one addition)
   int offR3[3], offT3[3];
 #pragma unroll
   for (int u = 0; u < 3; u++) {
     const int tap = 32 * u + li;
     const int dy = tap < K1 ? tap / F1 : 0, dx = tap < K1 ? tap - dy * F1 : 0;
-    offR3[u] = 3 * (dy * L.rs + dx);
-    offT3[u] = 3 * (dx * L.st + dy);
+    offR3[u] = 12 * (dy * L.rs + dx);
+    offT3[u] = 12 * (dx * L.st + dy);
   }
-  const int spec = li == K1 - 64 ? L.cst / 4 : li > K1 - 64 ? L.cst / 4 + 16 : -1;
+  // (these addresses are LDS addresses, the region's own included, so that
+  // nothing is left to add after the per-part addresses below)
+  typedef __attribute__((address_space(3))) const uint32_t lds_u32;
+  const int lds0 = (int)(uintptr_t)(__attribute__((address_space(3))) char*)base;
+  const int spec = li == K1 - 64 ? lds0 + L.cst : li > K1 - 64 ? lds0 + L.cst + 64 : -1;
 
   f32x16 g1[2][3], g2[2];
 #pragma unroll
@@ -325,8 +359,19 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     for (int u = 0; u < 3; u++) g1[t][u] = zero16();
   }
   float gb2 = 0.0f;
+  // kTr: delta2's running sums in the row layout (register r <-> channel
+  // crow(r, h), this lane's slot over the wave's items)
+  float gbr[16];
+#pragma unroll
+  for (int r = 0; r < 16; r++) gbr[r] = 0.0f;
 
   float* const sc = smem + L.sc / 4 + wave * kD6Sc;
+  // kTr: this wave's part image in the sc region: the lane's write address of
+  // either k-step and its transposed-read address (d6tr.hpp)
+  char* const trw = base + L.sc + d6tr_wave_off(wave);
+  char* const trw0 = trw + d6tr_write_off(li, h, 0, 0, 0);
+  char* const trw1 = trw + d6tr_write_off(li, h, 1, 0, 0);
+  const char* const trr = trw + d6tr_read_off(lane, 0, 0, 0);
   const uint16_t* const wl2 = reinterpret_cast<const uint16_t*>(w2i) + lane * 8;
 
   // The block's chunks form one stream (sample j of the block = blockIdx.x +
@@ -349,8 +394,9 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   f32x4 d2r[4], a1r[2][4];
   uint32_t d2m = 0, d2raw = 0;
   int d2pix = 0;
-  auto ld_d2 = [&](int j, int c) {
-    const int pix = slots[c * 32 + li];
+  // (sv: kTr, the slot's table dword, read by the caller for its delta3 offset too)
+  auto ld_d2 = [&](int j, int c, int sv) {
+    const int pix = kTr ? d6_slot_pix(sv) : slots[c * 32 + li];
     if constexpr (kD3) {
       // (only the load here; the select and shift wait for it at the use)
       d2pix = pix;
@@ -435,6 +481,34 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       a[q] = *reinterpret_cast<const bf16x8*>(w3l + (s_ * 3 + q) * 512);
     }
   };
+  // kTr: da[k]'s parts into the wave's image, then db[m] out of it
+  auto tr_write = [&](int k) __attribute__((always_inline)) {
+    char* const p = k ? trw1 : trw0;
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const u32x4 d = __builtin_bit_cast(u32x4, da[k][q]);
+      *reinterpret_cast<uint2*>(p + q * kD6TrPartRow) = uint2{d[0], d[1]};
+      *reinterpret_cast<uint2*>(p + q * kD6TrPartRow + 16) = uint2{d[2], d[3]};
+    }
+  };
+  auto tr_read = [&](int m) __attribute__((always_inline)) {
+    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const char* const p = trr + 16 * m * kD6TrRow + q * kD6TrPartRow;
+      const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p));
+      const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + 8 * kD6TrRow));
+      db[m][q] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+  };
+  // (f = 1 for an item that will run, 0 for the one past the block's last:
+  // its delta2 is formed like any other, from a stale delta3 image; x * 1 + s
+  // rounds once, as the addition)
+  auto sum_d2 = [&](float f) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) gbr[r] = __builtin_fmaf(d2v[r], f, gbr[r]);
+  };
   // in pieces, so phase C can spread them over its MFMA groups: 0 the
   // transposed reads, 1-2 da, 3-4 db (+ gbs)
   float d2t[16];
@@ -497,19 +571,34 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   item(ki, kj, kc);
   __syncthreads();  // tables (kD3: and the first delta3 image)
   w2read0();
-  ld_d2(kj, kc);
-  ld_a1(kj, kc);
-  if constexpr (kD3) {
-    bf16x8 ga[3], gb[3];
-    const int t = d3tab_[kc * 32 + li];
-    d3read(kj, t, 0, ga, gb);
-    d2gemm(kj, t, ga, gb);
-  } else {
-    take_rows();
+  {
+    const int sv = kD3 ? d3tab_[kc * 32 + li] : 0;
+    ld_d2(kj, kc, sv);
+    ld_a1(kj, kc);
+    if constexpr (kD3) {
+      bf16x8 ga[3], gb[3];
+      const int t = kTr ? d6_slot_off(sv) : sv;
+      d3read(kj, t, 0, ga, gb);
+      d2gemm(kj, t, ga, gb);
+    } else {
+      take_rows();
+    }
   }
-  stage_d2();
+  if constexpr (kTr) {
+    sum_d2(1.0f);
 #pragma unroll
-  for (int piece = 0; piece < 5; piece++) split_d2(piece);
+    for (int k = 0; k < 2; k++) {
+      split_d2(1 + k);
+      tr_write(k);
+    }
+    __builtin_amdgcn_wave_barrier();
+    tr_read(0);
+    tr_read(1);
+  } else {
+    stage_d2();
+#pragma unroll
+    for (int piece = 0; piece < 5; piece++) split_d2(piece);
+  }
 
   // Each item runs as three phases whose MFMAs carry the VALU work of the
   // next phase or item (one wave per SIMD: nothing else covers it):
@@ -567,16 +656,27 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       // (the next item's loads go out in VMEM slots of the MFMA patterns:
       // left alone, the scheduler sank them to just before their first use;
       // issued between the phases they cost ~10% of an item)
-      gb2 += gbs;
-      if constexpr (!kD3) ld_d2(nj, nc);
-      int rc4[2][2];  // run codes of this lane's half: k-step m takes runs 4m + h, 4m + 2 + h
+      if constexpr (!kTr) gb2 += gbs;
+      if constexpr (!kD3) ld_d2(nj, nc, 0);
+      // run codes of this lane's half (k-step m takes runs 4m + h, 4m + 2 +
+      // h) as the runs' base byte addresses in this sample's X images and
+      // their orientation, once per item: the R / T choice and the ~code were
+      // redone for each of gW1's six steps
+      const u32x4 rc4 = *reinterpret_cast<const u32x4*>(runs + 8 * c + 4 * h);
+      int xrb[2][2];
+      bool xrt[2][2];
 #pragma unroll
       for (int m = 0; m < 2; m++)
 #pragma unroll
-        for (int e = 0; e < 2; e++) rc4[m][e] = runs[8 * c + 4 * m + 2 * e + h];
-      const int d3t = kD3 ? d3tab_[nc * 32 + li] : 0;  // the next item's
+        for (int e = 0; e < 2; e++) {
+          const int code = (int)rc4[2 * m + e];
+          xrt[m][e] = code < 0;
+          xrb[m][e] = lds0 + 4 * (xo + (code < 0 ? ~code : code));
+        }
+      const int d3s = kD3 ? d3tab_[nc * 32 + li] : 0;  // the next item's
+      const int d3t = kTr ? d6_slot_off(d3s) : d3s;
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (kD3) ld_d2(nj, nc);
+      if constexpr (kD3) ld_d2(nj, nc, d3s);
       f32x16 d1[2] = {zero16(), zero16()};
       {
         bf16x8 b0[3], b1[3];
@@ -650,13 +750,18 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
         u32x4 d[3];
 #pragma unroll
         for (int e = 0; e < 2; e++) {
-          const int code = rc4[m][e];
-          int a = xo + (code >= 0 ? code + offR3[u] : ~code + offT3[u]);
+          int a = xrb[m][e] + (xrt[m][e] ? offT3[u] : offR3[u]);
           if (u == 2) a = spec >= 0 ? spec : a;
+          // (a part's two dwords are one ds_read2_b32 into its operand's
+          // register pair only with an address of the part's own: from one
+          // address the six were paired by offset, across the parts, and each
+          // operand then took two moves to assemble, 36 per item)
+          int aq[3] = {a, a + 4, a + 8};
+          asm("" : "+v"(aq[1]), "+v"(aq[2]));
 #pragma unroll
           for (int q = 0; q < 3; q++) {
-            d[q][2 * e] = u32[a + q];
-            d[q][2 * e + 1] = u32[a + q + 6];
+            d[q][2 * e] = *(lds_u32*)(uintptr_t)(unsigned)aq[q];
+            d[q][2 * e + 1] = *(lds_u32*)(uintptr_t)(unsigned)(aq[q] + 24);
           }
         }
 #pragma unroll
@@ -708,7 +813,28 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
         else
           w2read0();  // the next item's phase A
         mma_x6_2(dx[m][0], bx[st & 1], g1[0][u], dx[m][1], bx[st & 1], g1[1][u]);
-        if (kD3) {
+        if (kTr) {
+          // step 0: the delta2 sum and relu' mask, 1-2: da and its parts into
+          // the image, 3: gB2's sums and the transposed reads of db
+          if (st == 0) {
+            mask_take();
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+              const float v = gacc[0][r] + gacc[1][r];
+              d2v[r] = mask_d2(r, v);
+            }
+          }
+          if (st == 1 || st == 2) {
+            split_d2(st);
+            tr_write(st - 1);
+          }
+          if (st == 3) {
+            sum_d2((int)blockIdx.x + nj * (int)gridDim.x < g.batch ? 1.0f : 0.0f);
+            __builtin_amdgcn_wave_barrier();
+            tr_read(0);
+            tr_read(1);
+          }
+        } else if (kD3) {
           // step 0: the delta2 sum, relu' mask and rows into the transpose
           // scratch, 1: the transposed reads and da, 2: da, 3-4: db (+ gbs)
           if (st == 0) {
@@ -796,13 +922,29 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     }
     __syncthreads();
   }
-  red[wave * 64 + lane] = gb2;
-  __syncthreads();
-  if (wave == 0) {
+  if constexpr (kTr) {
+    // gB2[n]: the lanes' sums of channel n = crow(r, h) over the four waves
+    // and 32 slots, in one fixed order per channel (slots from n on, so the 32
+    // channels' reads fall on 32 banks)
 #pragma unroll
-    for (int w = 1; w < 4; w++) gb2 += red[w * 64 + lane];
-    gb2 += __shfl_xor(gb2, 32, 64);
-    if (h == 0) stg[NW1 + N1 + NW2 + li] = gb2;
+    for (int r = 0; r < 16; r++) red[(wave * 16 + r) * 64 + lane] = gbr[r];
+    __syncthreads();
+    if (threadIdx.x < N2) {
+      const int n = threadIdx.x, r = (n & 3) + 4 * (n >> 3), hn = (n >> 2) & 1;
+      float v = 0.0f;
+      for (int w = 0; w < 4; w++)
+        for (int i = 0; i < 32; i++) v += red[(w * 16 + r) * 64 + 32 * hn + ((i + n) & 31)];
+      stg[NW1 + N1 + NW2 + n] = v;
+    }
+  } else {
+    red[wave * 64 + lane] = gb2;
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int w = 1; w < 4; w++) gb2 += red[w * 64 + lane];
+      gb2 += __shfl_xor(gb2, 32, 64);
+      if (h == 0) stg[NW1 + N1 + NW2 + li] = gb2;
+    }
   }
   __syncthreads();
   static_assert(N1 == 64 && P12 % 4 == 0, "16 quads per slab row");

@@ -351,6 +351,7 @@ __global__ __launch_bounds__(256, 2) void l12_fwd_kernel(
 
 #include "runs.hpp"
 #include "d3taps.hpp"
+#include "d6tr.hpp"
 #include "l12x6.hpp"
 #include "d1x6.hpp"
 #include "l3_delta.hpp"
@@ -926,6 +927,7 @@ struct StepPlan {
   // delta2 (d1x6.hpp kD3).  kD1c: the fp32 delta1 kernel is d1c, split over
   // d1c_parts ranges of chunks per sample.
   bool x6, l3r, l3_fused, d3mode, kD1c;
+  bool d1tr;                 // d3mode: d1x6 with the delta2 part images (D6Lds::tr)
   int d1c_parts;
   RunGeom rg;
   int g12, g3, gd;           // grids of l12, layer 3 and delta1 (one slab per block of the last two)
@@ -982,7 +984,11 @@ static bool plan_step(uint32_t w, uint32_t h, uint32_t batch, int arith, StepPla
   const int gdf = p.kD1c ? (int)std::min<size_t>((size_t)batch * p.d1c_parts, kD1cGrid) : grid_for_batch(batch, 512);
   p.gd = p.x6 ? gd6 : gdf;
   p.lds12 = p.x6 ? X6Lds(w, h).bytes : 0;
-  p.ldsd = p.x6 ? D6Lds(w, h, p.rg, p.d3mode).bytes : p.kD1c ? d1c_lds_bytes(w, h) : 0;
+  const D6Lds ld6(w, h, p.rg, p.d3mode);
+  p.ldsd = p.x6 ? ld6.bytes : p.kD1c ? d1c_lds_bytes(w, h) : 0;
+  // d1x6 in delta3 mode: its form with the delta2 part images (d6tr.hpp) where
+  // D6Lds has room for them
+  p.d1tr = p.x6 && p.d3mode && ld6.tr;
   // (the workspace holds either arithmetic's slabs: srcnn_set_arith between
   // the size query and the step needs no new query)
   p.s12 = (size_t)std::max(gd6, gdf) * NetT::P12;
@@ -1065,12 +1071,14 @@ static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, 
   }
   {
     SRCNN_PROFILE("delta1_grad12_fused", s);
-    kernels_note(p.x6 ? (p.d3mode ? "d1x6_d3" : "d1x6_grad12") : p.kD1c ? "d1c_grad12" : "d1_grad12");
+    // (d1x6_d3: the form with the part images; d1x6_d3_sc: the fp32 scratch form)
+    kernels_note(p.x6 ? (p.d1tr ? "d1x6_d3" : p.d3mode ? "d1x6_d3_sc" : "d1x6_grad12") : p.kD1c ? "d1c_grad12" : "d1_grad12");
     const dim3 grid(p.gd), blk(256);
     const D3Geom dg{w3, h3, F3};
     // d1x6<true>: D2 holds delta3 and M2 the mask; A2 is not read then
-    int rc = p.x6 ? (p.d3mode ? launch(d1x6_grad12_kernel<true>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg)
-                              : launch(d1x6_grad12_kernel<false>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg))
+    int rc = p.x6 ? (p.d1tr     ? launch(d1x6_grad12_kernel<true, true>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg)
+                     : p.d3mode ? launch(d1x6_grad12_kernel<true>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg)
+                                : launch(d1x6_grad12_kernel<false>, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg))
              : p.kD1c ? launch(d1c_grad12_kernel<9>, grid, dim3(256 * kD1cTeams), p.ldsd, s, X, A1, D2, P.W2, slab12, g,
                                d1c_xs_floats(h), p.d1c_parts)
                       : launch(d1_grad12_kernel<N1, N2, F1>, grid, blk, 0, s, X, A1, D2, P.W2, slab12, g);
@@ -1121,8 +1129,9 @@ int preload(const srcnn_net* net) {
                        (const void*)slab_reduce_kernel, (const void*)l3r_delta_kernel<N::F3, false>,
                        (const void*)l3r_delta_kernel<N::F3, true>, (const void*)d1c_grad12_kernel<9>,
                        (const void*)l12x6_fwd_kernel<false>, (const void*)l12x6_fwd_kernel<true>,
-                       (const void*)d1x6_grad12_kernel<false>, (const void*)d1x6_grad12_kernel<true>};
-    const int rc = resolve_kernels(k, N::kDefault12 ? 12 : 7);
+                       (const void*)d1x6_grad12_kernel<false>, (const void*)d1x6_grad12_kernel<true>,
+                       (const void*)d1x6_grad12_kernel<true, true>};
+    const int rc = resolve_kernels(k, N::kDefault12 ? 13 : 7);
     return rc ? rc : 1;
   });
 }
