@@ -383,6 +383,20 @@ int srcnn_gather_tiles(const float* plane, uint32_t pw, uint32_t ph, uint32_t x0
                              as_stream(stream));
 }
 
+int srcnn_gather_batch(const srcnn_plane_pair* planes, uint32_t n_planes,
+                       const srcnn_tile_ref* refs, uint32_t n, uint32_t tw, uint32_t th, float* X,
+                       float* T, float* means, srcnn_stream_t stream) {
+  SRCNN_REQUIRE(planes && refs && X && T, "gather_batch: null buffer");
+  SRCNN_REQUIRE(n_planes > 0 && tw > 0 && th > 0, "gather_batch: n_planes(%u) and tile %ux%u must be > 0",
+                n_planes, tw, th);
+  SRCNN_REQUIRE((uint64_t)tw * th <= 0x7fffffffull,
+                "gather_batch: tile %ux%u exceeds the kernel's 32-bit index: its floats must number at "
+                "most 2^31-1",
+                tw, th);
+  if (n == 0) return SRCNN_OK;
+  return srcnn::gather_batch(planes, n_planes, refs, n, tw, th, X, T, means, as_stream(stream));
+}
+
 size_t srcnn_make_pairs_count(uint32_t W, uint32_t H, uint32_t scale, uint32_t tile,
                               uint32_t stride, uint32_t* nx, uint32_t* ny) {
   if (nx) *nx = 0;

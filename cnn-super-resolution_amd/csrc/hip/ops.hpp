@@ -260,6 +260,13 @@ int downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H, 
 int gather_tiles(const float* plane, uint32_t pw, uint32_t x0, uint32_t y0, uint32_t stride,
                  uint32_t nx, uint32_t ny, uint32_t tw, uint32_t th, int sub_mean, float* tiles,
                  float* means, hipStream_t s);
+// one workgroup per record of refs [n] (device): the record's footprint of
+// planes[ref.plane] (device table) through orientation ref.op into X, T
+// [n][th][tw], X minus the footprint's mean; an invalid record gives NaN tiles
+// 
+int gather_batch(const srcnn_plane_pair* planes, uint32_t n_planes, const srcnn_tile_ref* refs,
+                 uint32_t n, uint32_t tw, uint32_t th, float* X, float* T, float* means,
+                 hipStream_t s);
 int preload_pairs();
 // quality.hip: {mse, psnr, ssim} of the luma of two Ws x Hs windows (a, b: the
 // window's first pixel; SRCNN_PIX_* formats; pitches in pixels) into result

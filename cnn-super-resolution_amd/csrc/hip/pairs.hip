@@ -5,6 +5,9 @@
 //   gather_tiles    float plane [ph][pw] -> a grid of tiles [n][th][tw], each
 //                   optionally minus its own mean (the batch layout
 //                   srcnn_train_fwd_bwd reads)
+//   gather_batch    planes + a device-side list of {plane, origin, orientation}
+//                   records -> the X and T batches of one training chunk, in
+//                   one launch
 // The reference has no counterpart: its pairs are made on the host, one file
 // per sample.  The resampling is specified in DESIGN.md 11.1.
 //
@@ -158,6 +161,104 @@ __global__ __launch_bounds__(kThreads) void gather_tiles_kernel(
   }
 }
 
+// gather_batch: one workgroup per record of a device-side list
+// {plane, x, y, op}; the X tile (minus the footprint's mean) and the T tile
+// leave through one of the eight orientations.  The footprint is sw x sh =
+// tw x th, swapped when op transposes.  Its mean is gather_tiles' sum with
+// (tw, th) := (sw, sh): thread t adds the footprint's elements t, t + 256, ...
+// in its own row-major order whatever op says, so the loop that fetches the
+// footprint is the loop that sums it.
+//
+// Footprints of at most kStage floats (rows padded to an odd pitch) are staged
+// in LDS, X and T together, all loads in flight before the one barrier: the
+// loads run along the footprint's rows, the stores along the tile's rows, and
+// a transposing op turns into LDS reads at a stride of the odd pitch, which
+// puts any 32 (or 64) consecutive lanes on as many different banks.  8 KB per
+// plane: a 45 x 45 footprint fits, and eight workgroups a CU keep their 16 KB
+// each with LDS to spare.  Larger footprints read the plane through the
+// permutation, a strided read when op transposes, as gather_tiles would.
+constexpr uint32_t kStage = 2048;
+
+__device__ __forceinline__ uint32_t batch_src(uint32_t e, uint32_t tw, uint32_t sw, uint32_t sh,
+                                              uint32_t op, uint32_t* b) {
+  const uint32_t r = e / tw, c = e - r * tw;
+  uint32_t a = op & 4 ? c : r;
+  *b = op & 4 ? r : c;
+  if (op & 2) a = sh - 1 - a;
+  if (op & 1) *b = sw - 1 - *b;
+  return a;
+}
+
+__global__ __launch_bounds__(kThreads) void gather_batch_kernel(
+    const srcnn_plane_pair* __restrict__ planes, uint32_t n_planes,
+    const srcnn_tile_ref* __restrict__ refs, uint32_t tw, uint32_t th, float* __restrict__ X,
+    float* __restrict__ T, float* __restrict__ means) {
+  __shared__ float s_x[kStage], s_t[kStage];
+  __shared__ float s_part[kThreads / 64];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n = tw * th;  // <= 2^31-1: e + 256 stays below 2^32
+  const srcnn_tile_ref ref = refs[blockIdx.x];
+  float* dx = X + (size_t)blockIdx.x * n;
+  float* dt = T + (size_t)blockIdx.x * n;
+  const uint32_t op = ref.op;
+  const uint32_t sw = op & 4 ? th : tw, sh = op & 4 ? tw : th;
+  bool ok = ref.plane < n_planes && op <= 7;
+  srcnn_plane_pair p = {};
+  if (ok) {
+    p = planes[ref.plane];
+    ok = (uint64_t)ref.x + sw <= p.w && (uint64_t)ref.y + sh <= p.h;
+  }
+  if (!ok) {  // (uniform over the workgroup) nothing of any plane is read
+    const float q = __builtin_nanf("");
+    for (uint32_t e = tid; e < n; e += kThreads) dx[e] = q, dt[e] = q;
+    if (means && tid == 0) means[blockIdx.x] = q;
+    return;
+  }
+  const float* sx = p.x + (size_t)ref.y * p.x_pitch + ref.x;
+  const float* st = p.t + (size_t)ref.y * p.t_pitch + ref.x;
+  const uint32_t lp = sw | 1;  // LDS row pitch: odd
+  const bool staged = (uint64_t)sh * lp <= kStage;
+
+  float acc = 0.0f;
+  if (staged) {
+    for (uint32_t e = tid; e < n; e += kThreads) {
+      const uint32_t r = e / sw, c = e - r * sw;
+      const float v = sx[(size_t)r * p.x_pitch + c];
+      s_t[r * lp + c] = st[(size_t)r * p.t_pitch + c];
+      s_x[r * lp + c] = v;
+      acc += v;
+    }
+  } else {
+    for (uint32_t e = tid; e < n; e += kThreads) {
+      const uint32_t r = e / sw, c = e - r * sw;
+      acc += sx[(size_t)r * p.x_pitch + c];
+    }
+  }
+  // gather_tiles' tree: the butterfly over the wave, then (0 + 1) + (2 + 3)
+#pragma unroll
+  for (int k = 32; k > 0; k >>= 1) acc += __shfl_xor(acc, k, 64);
+  if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+  __syncthreads();  // (also: the staged footprints are complete)
+  const float mean = ((s_part[0] + s_part[1]) + (s_part[2] + s_part[3])) / (float)n;
+  if (means && tid == 0) means[blockIdx.x] = mean;
+
+  if (staged) {
+    for (uint32_t e = tid; e < n; e += kThreads) {
+      uint32_t b;
+      const uint32_t a = batch_src(e, tw, sw, sh, op, &b);
+      dx[e] = s_x[a * lp + b] - mean;
+      dt[e] = s_t[a * lp + b];
+    }
+  } else {
+    for (uint32_t e = tid; e < n; e += kThreads) {
+      uint32_t b;
+      const uint32_t a = batch_src(e, tw, sw, sh, op, &b);
+      dx[e] = sx[(size_t)a * p.x_pitch + b] - mean;
+      dt[e] = st[(size_t)a * p.t_pitch + b];
+    }
+  }
+}
+
 }  // namespace
 
 int downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H, uint32_t scale,
@@ -196,11 +297,29 @@ int gather_tiles(const float* plane, uint32_t pw, uint32_t x0, uint32_t y0, uint
   return SRCNN_OK;
 }
 
+int gather_batch(const srcnn_plane_pair* planes, uint32_t n_planes, const srcnn_tile_ref* refs,
+                 uint32_t n, uint32_t tw, uint32_t th, float* X, float* T, float* means,
+                 hipStream_t s) {
+  SRCNN_PROFILE("gather_batch", s);
+  // one workgroup per record; a grid holds at most 2^31-1 of them
+  const uint32_t kMaxGrid = 0x7fffffffu;
+  const size_t tile = (size_t)tw * th;
+  for (uint32_t i = 0; i < n;) {
+    const uint32_t m = n - i < kMaxGrid ? n - i : kMaxGrid;
+    hipLaunchKernelGGL(gather_batch_kernel, dim3(m), dim3(kThreads), 0, s, planes, n_planes, refs + i,
+                       tw, th, X + i * tile, T + i * tile, means ? means + i : nullptr);
+    SRCNN_LAUNCH_TRY();
+    i += m;
+  }
+  return SRCNN_OK;
+}
+
 int preload_pairs() {
   const void* k[] = {(const void*)downscale_rgba_kernel<1>, (const void*)downscale_rgba_kernel<2>,
                      (const void*)downscale_rgba_kernel<3>, (const void*)downscale_rgba_kernel<4>,
-                     (const void*)gather_tiles_kernel<true>, (const void*)gather_tiles_kernel<false>};
-  return resolve_kernels(k, 6);
+                     (const void*)gather_tiles_kernel<true>, (const void*)gather_tiles_kernel<false>,
+                     (const void*)gather_batch_kernel};
+  return resolve_kernels(k, 7);
 }
 
 }  // namespace srcnn

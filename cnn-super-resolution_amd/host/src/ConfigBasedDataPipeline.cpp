@@ -365,9 +365,7 @@ float ConfigBasedDataPipeline::execute_batch(bool backprop, GpuAllocationPool& g
             "Sample without input / expected luma");
   }
   allocate_buffers(w, h);
-  LayerAllocationPool &l1 = gpu_alloc.layer_1, &l2 = gpu_alloc.layer_2, &l3 = gpu_alloc.layer_3;
-  bool flat = bind_flat(l1, l2, l3);
-  srcnn_net nt = net();
+  bool flat = bind_flat(gpu_alloc.layer_1, gpu_alloc.layer_2, gpu_alloc.layer_3);
   size_t tile_bytes = w * h * sizeof(float);
   float validation_error = 0.f;
   for (size_t i = 0; i < samples.size();) {
@@ -377,25 +375,121 @@ float ConfigBasedDataPipeline::execute_batch(bool backprop, GpuAllocationPool& g
       _context->copy_buffer(s.input_luma, _forward_gpu_buf, n * tile_bytes);
       _context->copy_buffer(s.expected_luma, _ground_truth_gpu_buf, n * tile_bytes);
     }
-    if (backprop && flat) {
-      size_t ws = srcnn_train_workspace_bytes(&nt, w, h, n);
-      void* wsp = scratch(ws);
-      srcnn::Context::Launch l(*_context, *_train_kernel);
-      check(srcnn_train_fwd_bwd(&nt, _context->fptr(_forward_gpu_buf), _context->fptr(_ground_truth_gpu_buf),
-                                w, h, n, _context->fptr(_flat_params), _context->fptr(_flat_grads),
-                                nullptr, wsp, ws, _context->stream()),
-            "execute_batch");
-    } else if (backprop) {
-      Event e = forward(l1, l2, l3, w, h, n);
-      backpropagate(l1, l2, l3, w, h, n, &e);
-    } else {
-      Event e = forward(l1, l2, l3, w, h, n);
-      float err = 0.f;
-      squared_error(_ground_truth_gpu_buf, w, h, n, _out_3_gpu_buf, gpu_nullptr, err,
-                    _config->total_padding(), &e);
-      validation_error += err;
-    }
-    _context->block();
+    validation_error += run_chunk(backprop, flat, gpu_alloc, w, h, n);
+    i += n;
+  }
+  return validation_error;
+}
+
+float ConfigBasedDataPipeline::run_chunk(bool backprop, bool flat, GpuAllocationPool& gpu_alloc, size_t w,
+                                         size_t h, size_t n) {
+  LayerAllocationPool &l1 = gpu_alloc.layer_1, &l2 = gpu_alloc.layer_2, &l3 = gpu_alloc.layer_3;
+  float err = 0.f;
+  if (backprop && flat) {
+    srcnn_net nt = net();
+    size_t ws = srcnn_train_workspace_bytes(&nt, w, h, n);
+    void* wsp = scratch(ws);
+    srcnn::Context::Launch l(*_context, *_train_kernel);
+    check(srcnn_train_fwd_bwd(&nt, _context->fptr(_forward_gpu_buf), _context->fptr(_ground_truth_gpu_buf),
+                              w, h, n, _context->fptr(_flat_params), _context->fptr(_flat_grads),
+                              nullptr, wsp, ws, _context->stream()),
+          "execute_batch");
+  } else if (backprop) {
+    Event e = forward(l1, l2, l3, w, h, n);
+    backpropagate(l1, l2, l3, w, h, n, &e);
+  } else {
+    Event e = forward(l1, l2, l3, w, h, n);
+    squared_error(_ground_truth_gpu_buf, w, h, n, _out_3_gpu_buf, gpu_nullptr, err,
+                  _config->total_padding(), &e);
+  }
+  _context->block();
+  return err;
+}
+
+ConfigBasedDataPipeline::TrainingGrid ConfigBasedDataPipeline::make_training_planes(ImageData& full,
+                                                                                    unsigned scale,
+                                                                                    size_t tile,
+                                                                                    size_t stride) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(scale >= 1 && scale <= 4, "make_training_planes: scale must be 1, 2, 3 or 4");
+  require(tile > 0 && tile <= 0xffffffffu && stride > 0 && stride <= 0xffffffffu,
+          "make_training_planes: tile and stride must be > 0");
+  require(full.w > 0 && full.h > 0, "make_training_planes: empty image");
+  require(_plane_tile == 0 || _plane_tile == tile, "make_training_planes: one tile size per run");
+  TrainingGrid g;
+  uint32_t nx = 0, ny = 0;
+  g.count = srcnn_make_pairs_count(full.w, full.h, scale, uint32_t(tile), uint32_t(stride), &nx, &ny);
+  if (g.count == 0) return g;
+  // (srcnn_make_pairs' own limits on the sizes)
+  require(srcnn_make_pairs_workspace_bytes(full.w, full.h, scale) > 0,
+          std::string("make_training_planes: ") + srcnn_last_error());
+  const uint32_t W = full.w, H = full.h, w = W / scale, h = H / scale, Wc = w * scale, Hc = h * scale;
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, W, H);
+  _context->write_image(rgba, full, true);
+  MemoryHandle small = _context->create_image(srcnn::MEM_READ_WRITE, w, h);
+  MemoryHandle xp = _context->allocate(srcnn::MEM_READ_WRITE, size_t(Wc) * Hc * sizeof(float));
+  MemoryHandle tp = _context->allocate(srcnn::MEM_READ_WRITE, size_t(W) * H * sizeof(float));
+  if (!_planes_kernel)
+    _planes_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "training_planes", 0, 0, 0, false,
+                                             "-D SCALE=" + std::to_string(scale));
+  {
+    srcnn::Context::Launch l(*_context, *_planes_kernel);
+    const uint8_t* src = static_cast<const uint8_t*>(_context->ptr(rgba));
+    uint8_t* sm = static_cast<uint8_t*>(_context->ptr(small));
+    check(srcnn_downscale_rgba(src, sm, W, H, scale, _context->stream()), "make_training_planes: downscale");
+    check(srcnn_upscale_luma(sm, _context->fptr(xp), w, h, scale, 0, _context->stream()),
+          "make_training_planes: upscale_luma");
+    check(srcnn_extract_luma(src, _context->fptr(tp), W, H, 1, _context->stream()),
+          "make_training_planes: extract_luma");
+  }
+  _context->block();  // (the two images are released below)
+  _context->raw_memory(small)->release();
+  _context->raw_memory(rgba)->release();
+  srcnn_plane_pair p;
+  p.x = _context->fptr(xp);
+  p.t = _context->fptr(tp);
+  p.x_pitch = Wc;
+  p.t_pitch = W;
+  p.w = Wc;
+  p.h = Hc;
+  g.nx = nx, g.ny = ny, g.plane = _plane_table.size(), g.w = Wc, g.h = Hc;
+  _plane_table.push_back(p);
+  _plane_tile = tile;
+  return g;
+}
+
+void ConfigBasedDataPipeline::upload_plane_table() {
+  require(!_plane_table.empty(), "upload_plane_table: no planes (make_training_planes kept none)");
+  const size_t bytes = _plane_table.size() * sizeof(srcnn_plane_pair);
+  _context->block();
+  if (_plane_table_gpu_buf != gpu_nullptr) _context->raw_memory(_plane_table_gpu_buf)->release();
+  _plane_table_gpu_buf = _context->allocate(srcnn::MEM_READ_WRITE, bytes);
+  _context->write_buffer(_plane_table_gpu_buf, 0, bytes, _plane_table.data(), true);
+  _plane_table_uploaded = _plane_table.size();
+}
+
+float ConfigBasedDataPipeline::execute_batch_refs(bool backprop, GpuAllocationPool& gpu_alloc,
+                                                  const std::vector<srcnn_tile_ref>& refs) {
+  if (refs.empty() || _mini_batch_size == 0) throw std::runtime_error("Batch cannot be empty");
+  check_initialized(backprop ? (LOAD_KERNEL_LAYERS | LOAD_KERNEL_BACKPROPAGATE)
+                             : (LOAD_KERNEL_LAYERS | LOAD_KERNEL_MISC));
+  require(_plane_table_uploaded > 0 && _plane_table_uploaded == _plane_table.size(),
+          "execute_batch_refs: call upload_plane_table() after the last make_training_planes()");
+  const size_t w = _plane_tile, h = _plane_tile;
+  allocate_buffers(w, h);
+  bool flat = bind_flat(gpu_alloc.layer_1, gpu_alloc.layer_2, gpu_alloc.layer_3);
+  const size_t bytes = refs.size() * sizeof(srcnn_tile_ref);
+  if (_refs_gpu_buf == gpu_nullptr || _context->raw_memory(_refs_gpu_buf)->size < bytes) {
+    if (_refs_gpu_buf != gpu_nullptr) _context->raw_memory(_refs_gpu_buf)->release();
+    _refs_gpu_buf = _context->allocate(srcnn::MEM_READ_WRITE, bytes);
+  }
+  _context->write_buffer(_refs_gpu_buf, 0, bytes, refs.data(), true);
+  float validation_error = 0.f;
+  for (size_t i = 0; i < refs.size();) {
+    const size_t n = std::min(_mini_batch_size, refs.size() - i);
+    gather_batch(_plane_table_gpu_buf, _plane_table.size(), _refs_gpu_buf, i, n, w, h, _forward_gpu_buf,
+                 _ground_truth_gpu_buf);
+    validation_error += run_chunk(backprop, flat, gpu_alloc, w, h, n);
     i += n;
   }
   return validation_error;

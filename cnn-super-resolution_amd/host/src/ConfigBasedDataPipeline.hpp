@@ -122,6 +122,29 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * input_w = input_h = tile. */
   size_t make_training_pairs(ImageData& full, unsigned scale, size_t tile, size_t stride,
                              std::vector<SampleAllocationPool>& out);
+  /** The grid make_training_pairs would cut from an image (srcnn_make_pairs_count). */
+  struct TrainingGrid {
+    size_t nx = 0, ny = 0, count = 0;  // count = nx*ny; 0: the image holds no tile
+    size_t plane = 0;                  // index of the image's pair in the plane table
+    size_t w = 0, h = 0;               // the extent tiles may be cut from (Wc x Hc)
+  };
+  /** Planes instead of tiles: the image's degraded luma plane (down by
+   * `scale`, srcnn_upscale_luma with pad 0) and its ground-truth luma plane
+   * (srcnn_extract_luma, normalised) are made by the three plane calls
+   * srcnn_make_pairs starts with, into buffers that stay resident, and
+   * registered as one srcnn_plane_pair.  Returns the image's grid; count 0 (too
+   * small for one tile): nothing is kept.  Every call of a run takes the same
+   * `tile`. */
+  TrainingGrid make_training_planes(ImageData& full, unsigned scale, size_t tile, size_t stride);
+  /** the registered plane pairs to the device; call after the last make_training_planes */
+  void upload_plane_table();
+  size_t plane_count() const { return _plane_table.size(); }
+  /** execute_batch over samples named by records instead of held as tiles:
+   * the records are uploaded once, then every chunk of mini_batch_size() is
+   * one srcnn_gather_batch from the resident planes into the batch buffers,
+   * followed by the chunk execute_batch runs.  An invalid record gives NaN
+   * tiles, hence a NaN error / NaN gradients. */
+  float execute_batch_refs(bool backpropagate, GpuAllocationPool&, const std::vector<srcnn_tile_ref>&);
   /** "How many dB over bicubic?": the full-size ground truth in, the quality
    * of the net's x `scale` result (`net`) and of plain bicubic's (`bicubic`)
    * out, with `shave` pixels dropped per side: one srcnn_evaluate call on the
@@ -163,6 +186,9 @@ class ConfigBasedDataPipeline : public DataPipeline {
                 size_t h, size_t n);
   Event backpropagate(LayerAllocationPool&, LayerAllocationPool&, LayerAllocationPool&, size_t w,
                       size_t h, size_t n, Event* ev = nullptr);
+  /** one chunk of n samples of w x h already in the batch buffers: forward +
+   * (backprop ? gradient accumulation : squared error, which is returned) */
+  float run_chunk(bool backprop, bool flat, GpuAllocationPool&, size_t w, size_t h, size_t n);
   void fill_random_parameters(LayerData&, ParametersDistribution&, uint64_t seed);
   size_t load_parameters_file(const char* file);
 
@@ -198,6 +224,14 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
+  Kernel* _planes_kernel = nullptr;
+
+  // resident planes of make_training_planes and the records of the current epoch
+  std::vector<srcnn_plane_pair> _plane_table;
+  size_t _plane_tile = 0;
+  MemoryHandle _plane_table_gpu_buf = gpu_nullptr;
+  size_t _plane_table_uploaded = 0;
+  MemoryHandle _refs_gpu_buf = gpu_nullptr;
   Kernel* _evaluate_kernel = nullptr;
   Kernel* _update_all_kernel = nullptr;
   Kernel* _allreduce_kernel = nullptr;

@@ -286,6 +286,32 @@ Event DataPipeline::gather_tiles(MemoryHandle plane, size_t pw, size_t ph, size_
   return _context->mark();
 }
 
+Event DataPipeline::gather_batch(MemoryHandle planes, size_t n_planes, MemoryHandle refs, size_t first,
+                                 size_t n, size_t tw, size_t th, MemoryHandle X, MemoryHandle T,
+                                 MemoryHandle* means, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  const size_t lim = 0xffffffffu;
+  require(n_planes <= lim && n <= lim && tw <= lim && th <= lim, "gather_batch: argument beyond 32 bits");
+  auto holds = [this](MemoryHandle h, size_t bytes) {
+    return h != gpu_nullptr && _context->raw_memory(h)->is_usable() && _context->raw_memory(h)->size >= bytes;
+  };
+  require(holds(planes, n_planes * sizeof(srcnn_plane_pair)), "gather_batch: plane table smaller than n_planes");
+  require(holds(refs, (first + n) * sizeof(srcnn_tile_ref)), "gather_batch: record list smaller than first + n");
+  require(holds(X, n * tw * th * sizeof(float)) && holds(T, n * tw * th * sizeof(float)),
+          "gather_batch: X or T smaller than n tiles");
+  require(!means || holds(*means, n * sizeof(float)), "gather_batch: means smaller than n");
+  _context->wait(ev);
+  if (!_gather_batch_kernel)
+    _gather_batch_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "gather_batch");
+  srcnn::Context::Launch l(*_context, *_gather_batch_kernel);
+  check(srcnn_gather_batch(static_cast<const srcnn_plane_pair*>(_context->ptr(planes)), uint32_t(n_planes),
+                           static_cast<const srcnn_tile_ref*>(_context->ptr(refs)) + first, uint32_t(n),
+                           uint32_t(tw), uint32_t(th), _context->fptr(X), _context->fptr(T),
+                           means ? _context->fptr(*means) : nullptr, _context->stream()),
+        "gather_batch");
+  return _context->mark();
+}
+
 float DataPipeline::sum(MemoryHandle data, bool squared, Event* ev) {
   check_initialized(LOAD_KERNEL_MISC);
   _context->wait(ev);

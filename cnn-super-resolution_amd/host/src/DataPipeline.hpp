@@ -93,6 +93,15 @@ class DataPipeline {
                      size_t stride, size_t nx, size_t ny, size_t tw, size_t th, bool sub_mean,
                      MemoryHandle& tiles, MemoryHandle* means = nullptr, Event* ev = nullptr);
 
+  /** Extension: one batch of n tiles of tw x th floats gathered from resident
+   * plane pairs: `planes` holds n_planes srcnn_plane_pair entries, `refs`
+   * srcnn_tile_ref records, of which records [first, first + n) are taken;
+   * X (each tile minus its footprint's mean) and T must hold n*tw*th floats
+   * each, `means` (optional) n (srcnn_gather_batch). */
+  Event gather_batch(MemoryHandle planes, size_t n_planes, MemoryHandle refs, size_t first, size_t n,
+                     size_t tw, size_t th, MemoryHandle X, MemoryHandle T, MemoryHandle* means = nullptr,
+                     Event* ev = nullptr);
+
   /** Forward of one layer over `sample_count` samples (reference :358-410). */
   Event execute_layer(Kernel&, const LayerData&, LayerAllocationPool&, MemoryHandle& gpu_buf_in,
                       size_t input_w, size_t input_h, size_t sample_count,
@@ -166,6 +175,7 @@ class DataPipeline {
   Kernel* _upscale_compose_kernel = nullptr;
   Kernel* _downscale_kernel = nullptr;
   Kernel* _gather_tiles_kernel = nullptr;
+  Kernel* _gather_batch_kernel = nullptr;
   Kernel* _quality_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;

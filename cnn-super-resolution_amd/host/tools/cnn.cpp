@@ -5,6 +5,7 @@
 //       -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]
 //       [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]
 //       [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]
+//       [--device-batches] [--augment] [--random-origins]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -36,6 +37,16 @@
 //           --stride (defaults 33 and 14, the paper's sub-image size and
 //           stride), the input tiles degraded by exactly what `cnn upscale
 //           --scale S` applies at inference (srcnn_make_pairs).
+//           --device-batches keeps each image's two luma planes on the device
+//           instead of its tiles; every chunk of every epoch is then gathered
+//           from them by a list of {plane, origin, orientation} records in one
+//           launch (srcnn_gather_batch).  Same samples, same order, same
+//           parameters file.  --augment (a random one of the eight flips and
+//           rotations per training sample and epoch) and --random-origins (a
+//           random crop per training sample and epoch instead of its grid
+//           position) build on it; validation samples stay as they are.  Their
+//           draws come from a second generator seeded from --seed, so the
+//           shuffle and the split are the same with and without them.
 // Differences from the reference, on purpose: paths are joined with '/'
 // (the reference hard-codes "\\", src/Main_cl.cpp:284-287), the epoch
 // shuffle is seeded (--seed; the reference uses unseeded rand()).
@@ -84,6 +95,9 @@ struct Args {
   bool from_images = false;  // train --from-images: cut the pairs on the device
   size_t tile = 33, stride = 14;
   bool tile_set = false, stride_set = false;
+  bool device_batches = false;  // --from-images: keep planes, gather every chunk on the device
+  bool augment = false;         // ... with a random orientation per training sample and epoch
+  bool random_origins = false;  // ... with a random crop per training sample and epoch
   std::string config, in, out;
   std::string ref;       // quality: --ref
   unsigned shave = 0;    // quality, evaluate: --shave (evaluate: default --scale)
@@ -106,7 +120,8 @@ void usage() {
       << "usage: cnn [-h] [train | upscale | downscale | quality | evaluate] [dry] [profile]\n"
          "           -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]\n"
          "           [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
-         "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n\n"
+         "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n"
+         "           [--device-batches] [--augment] [--random-origins]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
@@ -142,6 +157,13 @@ void usage() {
          "                        --scale as the upscale mode resamples\n"
          "  --tile N              --from-images: sample size (default 33)\n"
          "  --stride N            --from-images: step between samples (default 14)\n"
+         "  --device-batches      --from-images: keep the images' luma planes on the device\n"
+         "                        instead of their tiles and gather every chunk from them\n"
+         "                        in one launch (same samples, same result)\n"
+         "  --augment             --from-images: a random flip / rotation (one of eight) per\n"
+         "                        training sample and epoch (implies --device-batches)\n"
+         "  --random-origins      --from-images: a random crop per training sample and epoch\n"
+         "                        instead of its grid position (implies --device-batches)\n"
          "  --seed N              seed of the random parameters and the epoch shuffles\n"
          "  --device D            HIP device index (default 0)\n"
          "  --devices N           train data-parallel on devices D .. D+N-1 (default 1)\n"
@@ -183,6 +205,9 @@ bool parse(int argc, char** argv, Args& a) {
       a.shave_set = true;
     }
     else if (s == "--from-images") a.from_images = true;
+    else if (s == "--device-batches") a.device_batches = true;
+    else if (s == "--augment") a.augment = true;
+    else if (s == "--random-origins") a.random_origins = true;
     else if (s == "--tile" || s == "--stride") {
       const std::string v = value(s.c_str());
       size_t n = 0;
@@ -230,6 +255,9 @@ bool parse(int argc, char** argv, Args& a) {
   if (a.from_images && !a.train) throw std::runtime_error("--from-images needs the train mode");
   if ((a.tile_set || a.stride_set) && !a.from_images)
     throw std::runtime_error("--tile and --stride need train --from-images");
+  if ((a.device_batches || a.augment || a.random_origins) && !a.from_images)
+    throw std::runtime_error("--device-batches, --augment and --random-origins need train --from-images");
+  if (a.augment || a.random_origins) a.device_batches = true;
   if (a.scale_set && !a.upscale && !a.downscale && !a.evaluate && !a.from_images)
     throw std::runtime_error(
         "--scale needs the upscale mode, the downscale mode, the evaluate mode or train --from-images");
@@ -449,9 +477,13 @@ int evaluate(ConfigBasedDataPipeline& p, const Args& a) {
 
 /** `train --from-images`: every file of the directory that decodes, in name
  * order, cut into sample pairs on the device (one srcnn_make_pairs call per
- * image) */
+ * image); with --device-batches the images' planes are kept instead
+ * (make_training_planes) and `grid` receives one record per sample, in the
+ * order the samples would have: image order, then grid index, op 0; `extent`
+ * the plane extent of each record's image */
 void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
-                       std::vector<SampleAllocationPool>& samples) {
+                       std::vector<SampleAllocationPool>& samples, std::vector<srcnn_tile_ref>& grid,
+                       std::vector<std::pair<uint32_t, uint32_t>>& extent) {
   DIR* d = opendir(a.in.c_str());
   if (!d) throw srcnn::IOException("cannot open images directory '" + a.in + "'");
   std::vector<std::string> names;
@@ -470,7 +502,17 @@ void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
       if (lead) std::cout << "'" << f << "' does not decode (" << e.what() << "). Skipping image" << std::endl;
       continue;
     }
-    const size_t n = p.make_training_pairs(img, a.scale, a.tile, a.stride, samples);
+    size_t n;
+    if (a.device_batches) {
+      const auto g = p.make_training_planes(img, a.scale, a.tile, a.stride);
+      n = g.count;
+      for (size_t i = 0; i < n; ++i) {
+        grid.push_back({uint32_t(g.plane), uint32_t(i % g.nx * a.stride), uint32_t(i / g.nx * a.stride), 0});
+        extent.push_back({uint32_t(g.w), uint32_t(g.h)});
+      }
+    } else {
+      n = p.make_training_pairs(img, a.scale, a.tile, a.stride, samples);
+    }
     if (n == 0) {
       if (lead)
         std::cout << "'" << f << "' (" << img.w << "x" << img.h << ") is too small for one " << a.tile << "x"
@@ -479,7 +521,10 @@ void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
     }
     ++images;
   }
-  if (lead) std::cout << "created " << samples.size() << " sample pairs from " << images << " images" << std::endl;
+  if (a.device_batches && !grid.empty()) p.upload_plane_table();
+  if (lead)
+    std::cout << "created " << (a.device_batches ? grid.size() : samples.size()) << " sample pairs from "
+              << images << " images" << std::endl;
 }
 
 /** Contiguous slice [start, start + count) of n items for `rank` of `world`
@@ -500,9 +545,11 @@ int train(ConfigBasedDataPipeline& p, const Args& a, uint64_t shuffle_seed, Grad
   const bool lead = rank == 0;
   GpuAllocationPool pools;
   std::vector<std::pair<std::string, std::string>> files;
-  if (a.from_images) pairs_from_images(p, a, lead, pools.samples);
+  std::vector<srcnn_tile_ref> grid;                    // --device-batches: the samples, as records
+  std::vector<std::pair<uint32_t, uint32_t>> extent;  // ... and the extent of each one's image
+  if (a.from_images) pairs_from_images(p, a, lead, pools.samples, grid, extent);
   else files = training_samples(a.in);
-  const size_t total = a.from_images ? pools.samples.size() : files.size();
+  const size_t total = a.device_batches ? grid.size() : a.from_images ? pools.samples.size() : files.size();
   if (total == 0) throw std::runtime_error("no training samples in '" + a.in + "'");
   const size_t nval = total * a.validation_percent / 100, ntrain = total - nval;
   if (lead) {
@@ -530,36 +577,76 @@ int train(ConfigBasedDataPipeline& p, const Args& a, uint64_t shuffle_seed, Grad
     ctx.raw_memory(s.expected_data)->release();
     pools.samples.push_back(s);
   }
-  const size_t px = pools.samples[0].input_w * pools.samples[0].input_h;
+  const size_t px = a.device_batches ? a.tile * a.tile : pools.samples[0].input_w * pools.samples[0].input_h;
 
   std::mt19937_64 rng(shuffle_seed);
-  std::vector<size_t> order(pools.samples.size());
+  // --augment / --random-origins draw from a generator of their own, so that
+  // the shuffle and the split do not depend on them; per epoch, for every
+  // training sample in the epoch's order (before sharding: every rank draws the
+  // same): x, then y (--random-origins), then op (--augment)
+  std::mt19937_64 aug_rng(shuffle_seed ^ 0x9e3779b97f4a7c15ull);
+  auto draw = [&aug_rng](uint64_t k) {  // uniform over 0 .. k-1, by rejection
+    const uint64_t lim = ~uint64_t(0) - ~uint64_t(0) % k;
+    uint64_t v;
+    do v = aug_rng();
+    while (v >= lim);
+    return uint32_t(v % k);
+  };
+  std::vector<size_t> order(total);
   bool error = false;
   for (size_t epoch = 0; epoch < a.epochs; ++epoch) {
     // new random validation / training split every epoch (src/Main_cl.cpp:244-261)
     for (size_t i = 0; i < order.size(); ++i) order[i] = i;
     std::shuffle(order.begin(), order.end(), rng);
+
     std::vector<SampleAllocationPool*> val, tr;
-    for (size_t i = 0; i < order.size(); ++i) (i < nval ? val : tr).push_back(&pools.samples[order[i]]);
+    std::vector<srcnn_tile_ref> rval, rtr;  // --device-batches: the two sets as records
+    if (a.device_batches) {
+      for (size_t i = 0; i < order.size(); ++i) {
+        srcnn_tile_ref r = grid[order[i]];
+        if (i >= nval) {
+          if (a.random_origins) {
+            r.x = draw(uint64_t(extent[order[i]].first) - a.tile + 1);
+            r.y = draw(uint64_t(extent[order[i]].second) - a.tile + 1);
+          }
+          if (a.augment) r.op = draw(8);
+        }
+        (i < nval ? rval : rtr).push_back(r);
+      }
+    } else {
+      for (size_t i = 0; i < order.size(); ++i) (i < nval ? val : tr).push_back(&pools.samples[order[i]]);
+    }
+    // forward (+ backpropagation) over `count` samples from `first` of the
+    // epoch's training (backprop) or validation set
+    auto execute = [&](bool backprop, size_t first, size_t count) {
+      if (a.device_batches) {
+        auto& set = backprop ? rtr : rval;
+        if (count == set.size()) return p.execute_batch_refs(backprop, pools, set);
+        std::vector<srcnn_tile_ref> mine(set.begin() + first, set.begin() + first + count);
+        return p.execute_batch_refs(backprop, pools, mine);
+      }
+      auto& set = backprop ? tr : val;
+      if (count == set.size()) return p.execute_batch(backprop, pools, set);
+      std::vector<SampleAllocationPool*> mine(set.begin() + first, set.begin() + first + count);
+      return p.execute_batch(backprop, pools, mine);
+    };
 
     if (comm) {
-      auto sh = shard(tr.size(), rank, world);
-      std::vector<SampleAllocationPool*> mine(tr.begin() + sh.first, tr.begin() + sh.first + sh.second);
-      if (!mine.empty()) p.execute_batch(true, pools, mine);
+      auto sh = shard(ntrain, rank, world);
+      if (sh.second) execute(true, sh.first, sh.second);
       p.allreduce_gradients(pools, *comm);
     } else {
-      p.execute_batch(true, pools, tr);
+      execute(true, 0, ntrain);
     }
-    p.update_parameters(pools.layer_1, pools.layer_2, pools.layer_3, tr.size());
+    p.update_parameters(pools.layer_1, pools.layer_2, pools.layer_3, ntrain);
 
-    if (!val.empty() && (epoch % 25 == 0 || epoch == a.epochs - 1)) {
+    if (nval && (epoch % 25 == 0 || epoch == a.epochs - 1)) {
       float err;
       if (comm) {
-        auto sh = shard(val.size(), rank, world);
-        std::vector<SampleAllocationPool*> mine(val.begin() + sh.first, val.begin() + sh.first + sh.second);
-        err = p.allreduce_sum(mine.empty() ? 0.f : p.execute_batch(false, pools, mine), *comm);
+        auto sh = shard(nval, rank, world);
+        err = p.allreduce_sum(sh.second ? execute(false, sh.first, sh.second) : 0.f, *comm);
       } else {
-        err = p.execute_batch(false, pools, val);
+        err = execute(false, 0, nval);
       }
       if (std::isnan(err)) {
         if (lead)
@@ -568,7 +655,7 @@ int train(ConfigBasedDataPipeline& p, const Args& a, uint64_t shuffle_seed, Grad
         error = true;
         break;
       }
-      float mean = err / val.size();
+      float mean = err / nval;
       if (lead)
         std::cout << "[" << epoch << "] mean validation error: " << mean << " (" << (mean / px)
                   << " per px)" << std::endl;
@@ -752,6 +839,11 @@ int main(int argc, char** argv) {
                                       ", stride " + std::to_string(a.stride) + "): "
                                 : std::string("Training samples directory: "))
               << a.in << std::endl
+              << (a.device_batches
+                      ? std::string("Batches gathered on the device from resident planes: ") +
+                            (a.random_origins ? "random origins" : "grid origins") + ", " +
+                            (a.augment ? "random orientations" : "orientation 0") + " for training samples\n"
+                      : std::string())
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   else if (a.downscale)
     std::cout << "Downscale mode, scale: " << a.scale << std::endl

@@ -86,6 +86,7 @@ SIGNATURES = {
     "srcnn_upscale_compose": (_I, [_P, _P, _P, _U, _U, _U, _P]),
     "srcnn_downscale_rgba": (_I, [_P, _P, _U, _U, _U, _P]),
     "srcnn_gather_tiles": (_I, [_P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _I, _P, _P, _P]),
+    "srcnn_gather_batch": (_I, [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P]),
     "srcnn_make_pairs_count": (_S, [_U, _U, _U, _U, _U, ctypes.POINTER(_U), ctypes.POINTER(_U)]),
     "srcnn_make_pairs_workspace_bytes": (_S, [_U, _U, _U]),
     "srcnn_make_pairs": (_I, [_P, _U, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
@@ -344,6 +345,42 @@ def gather_tiles(plane, pw, ph, x0, y0, stride, nx, ny, tw, th, sub_mean, tiles,
     which means [nx*ny] (may be None) then receives (srcnn_gather_tiles)."""
     _call("srcnn_gather_tiles", ptr(plane), pw, ph, x0, y0, stride, nx, ny, tw, th, int(sub_mean),
           ptr(tiles), ptr(means), s)
+
+
+def pack_plane_table(pairs):
+    """[(x, t, x_pitch, t_pitch, w, h), ...] (x, t: tensors or device
+    addresses) -> the srcnn_plane_pair table as a uint8 numpy array: 32 bytes
+    per entry, little-endian {u64 x, u64 t, u32 x_pitch, t_pitch, w, h}.
+    Upload it; the tensors must outlive its use."""
+    import numpy as np
+    table = np.zeros(len(pairs), dtype=np.dtype([("x", "<u8"), ("t", "<u8"), ("x_pitch", "<u4"),
+                                                 ("t_pitch", "<u4"), ("w", "<u4"), ("h", "<u4")]))
+    for i, (x, t, x_pitch, t_pitch, w, h) in enumerate(pairs):
+        table[i] = (ptr(x), ptr(t), x_pitch, t_pitch, w, h)
+    return table.view(np.uint8).reshape(-1)
+
+
+def pack_tile_refs(refs):
+    """[n][4] integers {plane, x, y, op} -> the srcnn_tile_ref records as a
+    uint8 numpy array: 16 bytes each, four little-endian u32."""
+    import numpy as np
+    a = np.asarray(refs)
+    if a.size == 0:
+        return np.zeros(0, np.uint8)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("pack_tile_refs: expected an array [n][4], got shape %s" % (a.shape,))
+    if (a < 0).any() or (a > 0xffffffff).any():
+        raise ValueError("pack_tile_refs: a field does not fit 32 unsigned bits")
+    return np.ascontiguousarray(a.astype("<u4")).view(np.uint8).reshape(-1)
+
+
+def gather_batch(planes, n_planes, refs, n, tw, th, X, T, means=None, s=None):
+    """planes (device srcnn_plane_pair table, pack_plane_table) and refs
+    (device srcnn_tile_ref records, pack_tile_refs) -> X, T [n][th][tw] f32:
+    record i's footprint through its orientation, X minus the footprint's
+    mean, which means [n] (may be None) receives; an invalid record gives NaN
+    tiles (srcnn_gather_batch)."""
+    _call("srcnn_gather_batch", ptr(planes), n_planes, ptr(refs), n, tw, th, ptr(X), ptr(T), ptr(means), s)
 
 
 def make_pairs_count(W, H, scale, tile, stride):

@@ -238,7 +238,61 @@ SRCNN_API int srcnn_gather_tiles(const float* plane, uint32_t pw, uint32_t ph, u
                                  uint32_t tw, uint32_t th, int sub_mean, float* tiles,
                                  float* means, srcnn_stream_t stream);
 
-/* One full-size image -> the (X, T) tile batches srcnn_train_fwd_bwd reads:
+/* One training chunk gathered straight from resident luma planes, in one
+ * launch (an MI355X extension; the reference packs a chunk with two buffer
+ * copies per sample, src/ConfigBasedDataPipeline.cpp:373-379): DESIGN.md 13 is
+ * the spec.  Both tables live in device memory and have fixed layouts: little-
+ * endian, the fields at the offsets their order gives, no padding (32 and 16
+ * bytes).
+ *
+ * srcnn_plane_pair: the two planes of one image cut at scale s: x = what
+ * srcnn_upscale_luma(small, W/s, H/s, s, pad = 0) writes (pitch Wc), t = what
+ * srcnn_extract_luma(rgba, normalize) writes (pitch W), w = Wc, h = Hc: the two
+ * planes srcnn_make_pairs builds in its workspace.
+ *
+ * srcnn_tile_ref: one sample.  The output tile is tw x th; op is an element of
+ * the dihedral group: bit 0 mirrors the footprint's columns, bit 1 its rows,
+ * bit 2 transposes afterwards (numpy: flip rows, flip columns, then .T).  The
+ * source footprint at (x, y) is sw x sh = tw x th, or th x tw when bit 2 is
+ * set; output element (r, c) takes the footprint's element (a', b'), where
+ * (a, b) = bit 2 ? (c, r) : (r, c), a' = bit 1 ? sh-1-a : a, b' = bit 0 ?
+ * sw-1-b : b.  X and T take the same permutation.
+ *
+ * X [n][th][tw]: each tile minus its footprint's mean, bit for bit the stated
+ * permutation of srcnn_gather_tiles(x plane, x0 = x, y0 = y, nx = ny = 1, tw =
+ * sw, th = sh, sub_mean = 1): the same fixed-order sum, over the footprint in
+ * its own row-major order, whatever op, the neighbouring records, their order
+ * or the pitches are.  T [n][th][tw]: the permutation of the t plane's values.
+ * means (device, [n], may be NULL) receives each record's mean.
+ *
+ * The records are device data, so they are checked on the device: a record
+ * with plane >= n_planes, op > 7, x + sw > w or y + sh > h (no 32-bit
+ * wrap-around in the sums) reads nothing of any plane and gets a tile of quiet
+ * NaNs in X and in T, and NaN in means.  Plane indexing is 64-bit: a plane of
+ * any size is legal.
+ *
+ * SRCNN_ERR_INVALID, before any launch: null planes, refs, X or T; n_planes,
+ * tw or th zero; tw*th beyond 2^31-1.  n = 0 is SRCNN_OK with no launch.
+ * Stream-ordered, no workspace; writes exactly the n*tw*th floats of X and of
+ * T and the n of means. */
+typedef struct {             /* 32 bytes */
+  const float* x;            /* degraded luma plane, [h][x_pitch] */
+  const float* t;            /* ground-truth luma plane, [>= h][t_pitch] */
+  uint32_t x_pitch, t_pitch; /* row pitches in floats, each >= w */
+  uint32_t w, h;             /* the extent tiles may be cut from, common to both */
+} srcnn_plane_pair;
+
+typedef struct {             /* 16 bytes */
+  uint32_t plane;            /* index into the plane table */
+  uint32_t x, y;             /* origin of the source footprint */
+  uint32_t op;               /* orientation, 0..7 */
+} srcnn_tile_ref;
+
+SRCNN_API int srcnn_gather_batch(const srcnn_plane_pair* planes, uint32_t n_planes,
+                                 const srcnn_tile_ref* refs, uint32_t n, uint32_t tw, uint32_t th,
+                                 float* X, float* T, float* means, srcnn_stream_t stream);
+
+/* One full-size image ->the (X, T) tile batches srcnn_train_fwd_bwd reads:
  * X [count][tile][tile] = the image degraded by exactly the resampling the
  * inference path applies (down by s, then srcnn_upscale_luma by s), each tile
  * minus its own mean; T [count][tile][tile] = the image's own luma.  The grid:
@@ -348,7 +402,9 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
  *     A3 extent; srcnn_train_activations: the three extents it documents;
  *     rgb: 3*W*H bytes; srcnn_make_pairs: count*tile*tile floats of X and of
- *     T each; srcnn_quality / srcnn_evaluate: the 3 / 6 doubles of result);
+ *     T each; srcnn_gather_batch, which takes no workspace: n*tw*th floats of
+ *     X and of T each and the n of means; srcnn_quality / srcnn_evaluate: the
+ *     3 / 6 doubles of result);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
