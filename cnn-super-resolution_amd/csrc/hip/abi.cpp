@@ -94,6 +94,51 @@ int up_dims(const char* who, uint32_t w, uint32_t h, uint32_t scale, uint32_t pa
   return SRCNN_OK;
 }
 
+// srcnn_yuv_* / srcnn_upscale_planes_u8: the sizes of one byte plane and of
+// its resampled counterpart against what the kernels of yuv.hip can index (int
+// coordinates, at most 2^31-1 elements in a plane; row offsets are size_t)
+int plane_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch) {
+  SRCNN_REQUIRE(w > 0 && h > 0, "%s: empty plane %ux%u", who, w, h);
+  SRCNN_REQUIRE(pitch >= w, "%s: pitch %u is below the row width %u", who, pitch, w);
+  SRCNN_REQUIRE((uint64_t)w * h <= 0x7fffffffull,
+                "%s: plane %ux%u exceeds the kernels' 32-bit index: a plane's elements must "
+                "number at most 2^31-1",
+                who, w, h);
+  return SRCNN_OK;
+}
+int yuv_range(const char* who, int range) {
+  SRCNN_REQUIRE(range == SRCNN_YUV_LIMITED || range == SRCNN_YUV_FULL,
+                "%s: range %d is neither SRCNN_YUV_LIMITED nor SRCNN_YUV_FULL", who, range);
+  return SRCNN_OK;
+}
+int yuv_luma_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch, uint32_t scale,
+                  uint32_t pad, UpDims* d) {
+  SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
+  if (int rc = plane_dims(who, w, h, pitch)) return rc;
+  const uint64_t lim = 0x7fffffffull;
+  const uint64_t W = (uint64_t)w * scale, H = (uint64_t)h * scale;
+  SRCNN_REQUIRE(W + pad <= lim && H + pad <= lim && (W + pad) * (H + pad) <= lim,
+                "%s: %ux%u x%u with padding %u exceeds the kernels' 32-bit index: the padded "
+                "plane's floats must number at most 2^31-1",
+                who, w, h, scale, pad);
+  d->W = (uint32_t)W;
+  d->H = (uint32_t)H;
+  d->PW = (uint32_t)(W + pad);
+  d->PH = (uint32_t)(H + pad);
+  return SRCNN_OK;
+}
+int planes_dims(const char* who, uint32_t src_pitch, uint32_t pw, uint32_t ph, uint32_t dst_pitch,
+                uint32_t ow, uint32_t oh, uint32_t scale) {
+  SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
+  if (int rc = plane_dims(who, pw, ph, src_pitch)) return rc;
+  if (int rc = plane_dims(who, ow, oh, dst_pitch)) return rc;
+  const uint64_t s = scale;
+  SRCNN_REQUIRE(s * (pw - 1) < ow && ow <= s * pw && s * (ph - 1) < oh && oh <= s * ph,
+                "%s: output %ux%u is not a crop of the x%u of %ux%u that keeps its last tile", who,
+                ow, oh, scale, pw, ph);
+  return SRCNN_OK;
+}
+
 // srcnn_downscale_rgba / srcnn_make_pairs: the source against the scale and
 // against what downscale_rgba_kernel can index (pixel offsets below 2^31)
 int down_dims(const char* who, uint32_t W, uint32_t H, uint32_t scale) {
@@ -367,6 +412,37 @@ int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* r
   return srcnn::upscale_compose(rgba, new_luma, rgb, w, h, scale, as_stream(stream));
 }
 
+int srcnn_yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
+                           uint32_t h, uint32_t scale, uint32_t pad, int range,
+                           srcnn_stream_t stream) {
+  UpDims d;
+  if (int rc = yuv_luma_dims("yuv_upscale_luma", w, h, pitch_y, scale, pad, &d)) return rc;
+  if (int rc = yuv_range("yuv_upscale_luma", range)) return rc;
+  SRCNN_REQUIRE(y && luma_padded, "yuv_upscale_luma: null buffer");
+  return srcnn::yuv_upscale_luma(y, pitch_y, luma_padded, w, h, scale, pad, range == SRCNN_YUV_FULL,
+                                 as_stream(stream));
+}
+
+int srcnn_upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch,
+                            uint32_t pw, uint32_t ph, uint8_t* dst0, uint8_t* dst1,
+                            uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t scale,
+                            srcnn_stream_t stream) {
+  if (int rc = planes_dims("upscale_planes_u8", src_pitch, pw, ph, dst_pitch, ow, oh, scale))
+    return rc;
+  SRCNN_REQUIRE(src0 && src1 && dst0 && dst1, "upscale_planes_u8: null buffer");
+  return srcnn::upscale_planes_u8(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh,
+                                  scale, as_stream(stream));
+}
+
+int srcnn_yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                           int range, srcnn_stream_t stream) {
+  if (int rc = plane_dims("yuv_compose_luma", W, H, pitch_y)) return rc;
+  if (int rc = yuv_range("yuv_compose_luma", range)) return rc;
+  SRCNN_REQUIRE(luma && y, "yuv_compose_luma: null buffer");
+  return srcnn::yuv_compose_luma(luma, y, pitch_y, W, H, range == SRCNN_YUV_FULL,
+                                 as_stream(stream));
+}
+
 int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
                          uint32_t scale, srcnn_stream_t stream) {
   if (int rc = down_dims("downscale_rgba", W, H, scale)) return rc;
@@ -498,7 +574,8 @@ int srcnn_preload(const srcnn_net* net) {
   int rc;
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
       (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0 ||
-      (rc = srcnn::preload_pairs()) < 0 || (rc = srcnn::preload_quality()) < 0)
+      (rc = srcnn::preload_pairs()) < 0 || (rc = srcnn::preload_quality()) < 0 ||
+      (rc = srcnn::preload_yuv()) < 0)
     return rc;
   return srcnn::preload_update();
 }
@@ -839,6 +916,74 @@ int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_
   if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
     return rc;
   return srcnn_upscale_compose(rgba, out, rgb, w, h, scale, stream);
+}
+
+// srcnn_upscale_yuv: every check that does not need the buffers; the chroma
+// sizes of the source (cw x ch) and of the output (CW x CH)
+struct YuvDims {
+  UpDims d;
+  uint32_t pad, cw, ch, CW, CH;
+};
+static int yuv_dims(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t cx, uint32_t cy,
+                    uint32_t scale, YuvDims* y) {
+  SRCNN_REQUIRE(net, "upscale_yuv: null srcnn_net");
+  size_t off[6];
+  if (int rc = srcnn_net_offsets(net, off)) return rc;
+  const uint64_t pad64 = (uint64_t)net->f1 + net->f2 + net->f3 - 3;
+  SRCNN_REQUIRE(pad64 <= 0x7fffffffull, "upscale_yuv: total padding %llu too large",
+                (unsigned long long)pad64);
+  y->pad = (uint32_t)pad64;
+  SRCNN_REQUIRE((cx == 2 && cy == 2) || (cx == 2 && cy == 1) || (cx == 1 && cy == 1),
+                "upscale_yuv: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)",
+                cx, cy);
+  if (int rc = yuv_luma_dims("upscale_yuv", w, h, w, scale, y->pad, &y->d)) return rc;
+  y->cw = (w - 1) / cx + 1;
+  y->ch = (h - 1) / cy + 1;
+  y->CW = (y->d.W - 1) / cx + 1;
+  y->CH = (y->d.H - 1) / cy + 1;
+  return SRCNN_OK;
+}
+
+size_t srcnn_upscale_yuv_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                         uint32_t scale) {
+  YuvDims y;
+  UpWs L;
+  if (yuv_dims(net, w, h, 1, 1, scale, &y)) return 0;
+  return up_ws(net, y.d, &L) ? L.total : 0;
+}
+
+int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst,
+                      uint32_t w, uint32_t h, uint32_t cx, uint32_t cy, uint32_t scale, int range,
+                      const float* params, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  YuvDims y;
+  if (int rc = yuv_dims(net, w, h, cx, cy, scale, &y)) return rc;
+  if (int rc = yuv_range("upscale_yuv", range)) return rc;
+  SRCNN_REQUIRE(src && dst && params && ws, "upscale_yuv: null buffer");
+  SRCNN_REQUIRE(src->y && src->u && src->v && dst->y && dst->u && dst->v,
+                "upscale_yuv: null plane");
+  // (the sizes again, now with the frames' pitches)
+  UpDims d;
+  if (int rc = yuv_luma_dims("upscale_yuv", w, h, src->pitch_y, scale, y.pad, &d)) return rc;
+  if (int rc = plane_dims("upscale_yuv", d.W, d.H, dst->pitch_y)) return rc;
+  if (int rc = planes_dims("upscale_yuv", src->pitch_c, y.cw, y.ch, dst->pitch_c, y.CW, y.CH, scale))
+    return rc;
+  UpWs L;
+  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "upscale_yuv: workspace %zu B < %zu B", ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  float* out = reinterpret_cast<float*>(p + L.out);
+  int rc;
+  if ((rc = srcnn_yuv_upscale_luma(src->y, src->pitch_y, plane, w, h, scale, y.pad, range, stream)))
+    return rc;
+  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_yuv_compose_luma(out, dst->y, dst->pitch_y, d.W, d.H, range, stream))) return rc;
+  return srcnn_upscale_planes_u8(src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v,
+                                 dst->pitch_c, y.CW, y.CH, scale, stream);
 }
 
 // regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |

@@ -1,5 +1,6 @@
 // keys.hpp -- the Keys cubic (a = -0.5) behind the constexpr weight tables of
-// upscale.hip and pairs.hip.
+// bicubic.hpp (upscale.hip and yuv.hip) and pairs.hip
+// (DESIGN.md 11.1).
 #pragma once
 
 namespace srcnn {

@@ -251,6 +251,19 @@ int upscale_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint
 int upscale_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
                     uint32_t scale, hipStream_t s);
 int preload_upscale();
+// yuv.hip: the same resampling for planar Y'CbCr frames: the Y
+// plane [h][w] u8 (pitch in bytes) into the padded plane as upscale_luma does,
+// normalised by the range; two u8 planes [ph][pw] bicubic x scale, rounded and
+// clamped, the top-left ow x oh of each into two u8 planes; the net's luma
+// [H][W] back into a Y plane
+int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                     uint32_t scale, uint32_t pad, bool full_range, hipStream_t s);
+int upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
+                      uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
+                      uint32_t oh, uint32_t scale, hipStream_t s);
+int yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                     bool full_range, hipStream_t s);
+int preload_yuv();
 // pairs.hip: antialiased bicubic / scale (1..4) of rgba [H][W][4] into small
 // [H/scale][W/scale][4], and the cut of a grid of nx x ny tiles (tw x th,
 // origin (x0, y0), step `stride`) out of a float plane of pitch pw into

@@ -245,6 +245,21 @@ int srcnn_free(void* ptr) {
   return SRCNN_OK;
 }
 
+int srcnn_host_alloc(void** ptr, size_t bytes) {
+  SRCNN_REQUIRE(ptr, "srcnn_host_alloc: null out pointer");
+  *ptr = nullptr;
+  if (bytes == 0) return SRCNN_OK;
+  hipError_t e = hipHostMalloc(ptr, bytes, hipHostMallocDefault);
+  if (e != hipSuccess)
+    return srcnn::fail(SRCNN_ERR_ALLOC, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  return SRCNN_OK;
+}
+
+int srcnn_host_free(void* ptr) {
+  if (ptr) SRCNN_HIP_TRY(hipHostFree(ptr));
+  return SRCNN_OK;
+}
+
 int srcnn_memcpy_h2d(void* dst, const void* src, size_t bytes, srcnn_stream_t stream) {
   if (bytes == 0) return SRCNN_OK;
   SRCNN_REQUIRE(dst && src, "srcnn_memcpy_h2d: null pointer");

@@ -255,6 +255,37 @@ void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, 
   _context->raw_memory(rgba)->release();
 }
 
+size_t ConfigBasedDataPipeline::super_resolve_yuv_workspace_bytes(unsigned w, unsigned h, unsigned scale) {
+  srcnn_net nt = net();
+  return srcnn_upscale_yuv_workspace_bytes(&nt, w, h, scale);
+}
+
+void ConfigBasedDataPipeline::super_resolve_yuv(const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst, unsigned w,
+                                                unsigned h, unsigned cx, unsigned cy, unsigned scale,
+                                                bool full_range, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_yuv needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  const int range = full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED;
+  if (stream) {
+    check(srcnn_upscale_yuv(&nt, &src, &dst, w, h, cx, cy, scale, range, _context->fptr(_flat_params), ws, ws_bytes,
+                            stream),
+          "upscale_yuv");
+    return;
+  }
+  if (!_upscale_yuv_kernel) {
+    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
+                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
+                             " -D F3=" + std::to_string(nt.f3);
+    _upscale_yuv_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_yuv", 0, 0, 0, false, args);
+  }
+  srcnn::Context::Launch l(*_context, *_upscale_yuv_kernel);
+  check(srcnn_upscale_yuv(&nt, &src, &dst, w, h, cx, cy, scale, range, _context->fptr(_flat_params), ws, ws_bytes,
+                          _context->stream()),
+        "upscale_yuv");
+}
+
 bool ConfigBasedDataPipeline::evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& q_net,
                                        QualityReport& q_bicubic) {
   check_initialized(LOAD_KERNEL_LAYERS);

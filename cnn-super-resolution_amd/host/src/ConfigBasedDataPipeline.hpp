@@ -112,6 +112,19 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * and reads the RGB result back.  Every output pixel passes through the
    * net: no border frame is left, also with scale 1. */
   void super_resolve(ImageData& low_res, unsigned scale, ImageData& result);
+  /** One planar Y'CbCr frame that is already on the device in, the frame of
+   * `scale` (1..4) times the size out: one srcnn_upscale_yuv call on the
+   * pipeline's flat parameters.  Only enqueues: no upload, no
+   * download, no allocation, no synchronisation, so a caller can keep several
+   * frames in flight, each with its own `stream`, workspace (`ws`, at least
+   * super_resolve_yuv_workspace_bytes) and device frames.  `stream` nullptr:
+   * the context's stream, and the call is counted (and in profile mode timed)
+   * as kernel 'srcnn_upscale_yuv'. */
+  void super_resolve_yuv(const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst, unsigned w, unsigned h,
+                         unsigned cx, unsigned cy, unsigned scale, bool full_range, void* ws, size_t ws_bytes,
+                         srcnn_stream_t stream = nullptr);
+  /** 0 if the net, the size or the scale is invalid (srcnn_last_error says why) */
+  size_t super_resolve_yuv_workspace_bytes(unsigned w, unsigned h, unsigned scale);
   /** Training pairs of one full-size image, cut on the device: one
    * srcnn_make_pairs call (the image degraded by the resampling super_resolve
    * applies: down by `scale`, bicubic up again; then a grid of tile x tile
@@ -223,6 +236,7 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _train_kernel = nullptr;
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
+  Kernel* _upscale_yuv_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
   Kernel* _planes_kernel = nullptr;
 

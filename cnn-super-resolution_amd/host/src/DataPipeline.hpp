@@ -75,6 +75,24 @@ class DataPipeline {
   Event upscale_compose(ImageData&, MemoryHandle gpu_buf_org_img, MemoryHandle gpu_buf_new_luma,
                         MemoryHandle& target, size_t scale, Event* ev = nullptr);
 
+  /** Extension, planar Y'CbCr: the Y plane `y` (w x h bytes,
+   * rows pitch_y bytes apart, already on the device) as upscale_luma's padded
+   * plane; full_range: Y / 255, else (Y - 16) / 219 (srcnn_yuv_upscale_luma). */
+  Event yuv_upscale_luma(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& gpu_buf_luma_padded,
+                         size_t scale, size_t total_padding, bool full_range, Event* ev = nullptr);
+
+  /** Extension: two byte planes of pw x ph (a frame's chroma) bicubic x
+   * `scale`, rounded and clamped, the top-left ow x oh of each into dst0 and
+   * dst1 (srcnn_upscale_planes_u8). */
+  Event upscale_planes_u8(MemoryHandle src0, MemoryHandle src1, size_t src_pitch, size_t pw, size_t ph,
+                          MemoryHandle dst0, MemoryHandle dst1, size_t dst_pitch, size_t ow, size_t oh,
+                          size_t scale, Event* ev = nullptr);
+
+  /** Extension: the net's luma (w x h floats) back into a Y plane
+   * (srcnn_yuv_compose_luma). */
+  Event yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y, bool full_range,
+                         Event* ev = nullptr);
+
   /** Extension, the inverse of the upscale: `img` antialiased-bicubic
    * downscaled by `scale` (1..4) on the device into `out`, RGBA of
    * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
@@ -173,6 +191,9 @@ class DataPipeline {
   Kernel* _swap_luma_kernel = nullptr;
   Kernel* _upscale_luma_kernel = nullptr;
   Kernel* _upscale_compose_kernel = nullptr;
+  Kernel* _yuv_upscale_luma_kernel = nullptr;
+  Kernel* _upscale_planes_u8_kernel = nullptr;
+  Kernel* _yuv_compose_luma_kernel = nullptr;
   Kernel* _downscale_kernel = nullptr;
   Kernel* _gather_tiles_kernel = nullptr;
   Kernel* _gather_batch_kernel = nullptr;

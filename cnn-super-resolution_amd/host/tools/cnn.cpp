@@ -5,7 +5,8 @@
 //       -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]
 //       [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]
 //       [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]
-//       [--device-batches] [--augment] [--random-origins]
+//       [--device-batches] [--augment] [--random-origins] [--frames N]
+//       [--range full|limited] [--slots N]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -15,6 +16,20 @@
 //           net and the composition all run on the device (srcnn_upscale), and
 //           every output pixel passes through the net.  --scale 1 is the
 //           "same size, no border frame" mode for inputs that are already scaled.
+//           If IN starts with the YUV4MPEG2 magic it is a Y4M video (8-bit
+//           4:2:0, 4:2:2 or 4:4:4, progressive) and is streamed: every frame
+//           is upscaled by S on the device as planar Y'CbCr -- luma through
+//           the net, chroma plain bicubic (srcnn_upscale_yuv) -- and OUT is a
+//           Y4M of S times the size with the same F, I, A, C and XCOLORRANGE
+//           tokens.  Two frame slots, each with its own stream, pinned host
+//           buffers, device frames and workspace: while one slot computes, the
+//           next frame is read into the other; a slot is drained and its frame
+//           written before it is reused, so frames leave in order (--slots 1:
+//           one slot).  --frames N stops after N frames; --range full|limited
+//           overrides the header's XCOLORRANGE (default limited).  A truncated
+//           frame ends the run with an error after the frames in front of it
+//           have been written.  With `profile` both slots use the pipeline's
+//           stream, so that the calls can be timed.
 // downscale: (extension) IN is a full-size image, OUT the image of 1/S the
 //           size (RGB), resampled on the device by the inverse of the upscale
 //           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
@@ -63,6 +78,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <mutex>
@@ -83,6 +99,7 @@
 #include "ConfigBasedDataPipeline.hpp"
 #include "Context.hpp"
 #include "Image.hpp"
+#include "Y4m.hpp"
 
 using namespace cnn_sr;
 
@@ -100,6 +117,11 @@ struct Args {
   bool random_origins = false;  // ... with a random crop per training sample and epoch
   std::string config, in, out;
   std::string ref;       // quality: --ref
+  size_t frames = 0;     // upscale, Y4M: --frames (0: all)
+  bool frames_set = false;
+  int range = -1;        // upscale, Y4M: --range (-1: the header's, 0 limited, 1 full)
+  unsigned slots = 2;    // upscale, Y4M: --slots
+  bool slots_set = false;
   unsigned shave = 0;    // quality, evaluate: --shave (evaluate: default --scale)
   bool shave_set = false;
   size_t epochs = 0;
@@ -121,13 +143,17 @@ void usage() {
          "           -c CONFIG -i IN [-o OUT] [-e EPOCHS] [--scale S] [--seed N] [--device D]\n"
          "           [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
          "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n"
-         "           [--device-batches] [--augment] [--random-origins]\n\n"
+         "           [--device-batches] [--augment] [--random-origins] [--frames N]\n"
+         "           [--range full|limited] [--slots N]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
          "  upscale               upscale mode: IN is a low-resolution image, OUT the image\n"
          "                        of --scale times the size (bicubic + net on the device;\n"
          "                        no un-enhanced border frame)\n"
+         "                        A Y4M video (YUV4MPEG2; 8-bit 4:2:0, 4:2:2 or 4:4:4) is\n"
+         "                        streamed frame by frame: luma through the net, chroma\n"
+         "                        bicubic, OUT a Y4M of --scale times the size\n"
          "  downscale             downscale mode: IN is a full-size image, OUT the image of\n"
          "                        1 / --scale the size (the inverse of the upscale mode's\n"
          "                        bicubic, on the device; -c is not needed)\n"
@@ -149,6 +175,10 @@ void usage() {
          "  --scale S             scale factor 1, 2, 3 or 4 (default 2; upscale, downscale,\n"
          "                        evaluate and train --from-images only; upscale 1: same\n"
          "                        size, every pixel through the net)\n"
+         "  --frames N            upscale, Y4M: stop after N frames\n"
+         "  --range full|limited  upscale, Y4M: the luma range (default: the header's\n"
+         "                        XCOLORRANGE, else limited)\n"
+         "  --slots N             upscale, Y4M: frames in flight, 1 or 2 (default 2)\n"
          "  --ref REF             quality: the image IN is measured against\n"
          "  --shave N             quality, evaluate: pixels dropped on every side before\n"
          "                        measuring (default: 0 for quality, --scale for evaluate)\n"
@@ -203,6 +233,30 @@ bool parse(int argc, char** argv, Args& a) {
         throw std::runtime_error("--shave must be a non-negative integer");
       a.shave = unsigned(n);
       a.shave_set = true;
+    }
+    else if (s == "--frames") {
+      const std::string v = value("--frames");
+      size_t n = 0, used = 0;
+      try {
+        n = std::stoul(v, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used != v.size() || v.empty() || v[0] == '-' || n == 0)
+        throw std::runtime_error("--frames must be a positive integer");
+      a.frames = n;
+      a.frames_set = true;
+    }
+    else if (s == "--range") {
+      const std::string v = value("--range");
+      if (v != "full" && v != "limited") throw std::runtime_error("--range must be full or limited");
+      a.range = v == "full";
+    }
+    else if (s == "--slots") {
+      const std::string v = value("--slots");
+      if (v != "1" && v != "2") throw std::runtime_error("--slots must be 1 or 2");
+      a.slots = unsigned(v[0] - '0');
+      a.slots_set = true;
     }
     else if (s == "--from-images") a.from_images = true;
     else if (s == "--device-batches") a.device_batches = true;
@@ -261,6 +315,8 @@ bool parse(int argc, char** argv, Args& a) {
   if (a.scale_set && !a.upscale && !a.downscale && !a.evaluate && !a.from_images)
     throw std::runtime_error(
         "--scale needs the upscale mode, the downscale mode, the evaluate mode or train --from-images");
+  if ((a.frames_set || a.range >= 0 || a.slots_set) && !a.upscale)
+    throw std::runtime_error("--frames, --range and --slots need the upscale mode");
   if (!a.ref.empty() && !a.quality) throw std::runtime_error("--ref needs the quality mode");
   if (a.shave_set && !a.quality && !a.evaluate)
     throw std::runtime_error("--shave needs the quality mode or the evaluate mode");
@@ -331,8 +387,122 @@ int forward(ConfigBasedDataPipeline& p, const Args& a) {
   return 0;
 }
 
-/** `cnn upscale`: the low-resolution image through srcnn_upscale */
+/** One frame in flight of `cnn upscale` on a Y4M stream: its own stream,
+ * pinned host buffers, device frames and workspace.  Everything is released
+ * when the slot goes, whatever ended the run. */
+struct FrameSlot {
+  srcnn_stream_t stream = nullptr;
+  void *host_in = nullptr, *host_out = nullptr;  // pinned
+  void *dev_in = nullptr, *dev_out = nullptr, *ws = nullptr;
+  srcnn_yuv_frame src{}, dst{};
+  bool busy = false;  // a frame is enqueued and not yet written
+
+  FrameSlot() = default;
+  FrameSlot(const FrameSlot&) = delete;
+  FrameSlot& operator=(const FrameSlot&) = delete;
+  ~FrameSlot() {
+    if (stream) srcnn_stream_sync(stream);
+    srcnn_free(dev_in);
+    srcnn_free(dev_out);
+    srcnn_free(ws);
+    srcnn_host_free(host_in);
+    srcnn_host_free(host_out);
+    if (stream) srcnn_stream_destroy(stream);
+  }
+  static srcnn_yuv_frame planes(void* base, const srcnn::y4m::Header& hd) {
+    uint8_t* b = static_cast<uint8_t*>(base);
+    return srcnn_yuv_frame{b, b + hd.luma_bytes(), b + hd.luma_bytes() + hd.chroma_bytes(), hd.w, hd.cw()};
+  }
+  void init(const srcnn::y4m::Header& in, const srcnn::y4m::Header& out, size_t ws_bytes, bool own_stream) {
+    if (own_stream) srcnn::check(srcnn_stream_create(&stream), "stream_create");
+    srcnn::check(srcnn_host_alloc(&host_in, in.frame_bytes()), "host_alloc");
+    srcnn::check(srcnn_host_alloc(&host_out, out.frame_bytes()), "host_alloc");
+    srcnn::check(srcnn_malloc(&dev_in, in.frame_bytes()), "malloc");
+    srcnn::check(srcnn_malloc(&dev_out, out.frame_bytes()), "malloc");
+    srcnn::check(srcnn_malloc(&ws, ws_bytes), "malloc");
+    src = planes(dev_in, in);
+    dst = planes(dev_out, out);
+  }
+};
+
+/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_yuv.  Any
+ * failed call throws, which ends the run before another frame is started. */
+int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
+  namespace y4m = srcnn::y4m;
+  y4m::Header hd = y4m::read_header(in);
+  if (a.range >= 0) {
+    hd.full_range = a.range == 1;
+    hd.has_range = true;
+  }
+  const y4m::Header ohd = hd.scaled(a.scale);
+  std::cout << "Y4M video: " << hd.w << "x" << hd.h << " C" << hd.chroma << ", "
+            << (hd.full_range ? "full" : "limited") << " range -> " << ohd.w << "x" << ohd.h << std::endl;
+  const size_t ws_bytes = p.super_resolve_yuv_workspace_bytes(hd.w, hd.h, a.scale);
+  srcnn::require(ws_bytes > 0, std::string("upscale: ") + srcnn_last_error());
+  std::ofstream out;
+  const bool store = !a.dry && !a.out.empty();
+  if (store) {
+    out.open(a.out, std::ios::binary);
+    if (!out) throw srcnn::IOException("cannot open '" + a.out + "' for writing");
+    y4m::write_header(out, ohd);
+  }
+  // profile mode: both slots on the pipeline's stream, where the calls are timed
+  const bool own_streams = !a.profile;
+  FrameSlot slots[2];
+  for (unsigned i = 0; i < a.slots; ++i) slots[i].init(hd, ohd, ws_bytes, own_streams);
+  auto stream_of = [&](FrameSlot& s) { return own_streams ? s.stream : p.context()->stream(); };
+  size_t written = 0;
+  // the slot's frame back to the host (the copy waits for the slot's work) and out
+  auto drain = [&](FrameSlot& s) {
+    if (!s.busy) return;
+    srcnn::check(srcnn_memcpy_d2h(s.host_out, s.dev_out, ohd.frame_bytes(), stream_of(s)), "memcpy_d2h");
+    s.busy = false;
+    if (store) y4m::write_frame(out, ohd, static_cast<const unsigned char*>(s.host_out));
+    ++written;
+  };
+  int rc = 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  size_t k = 0;
+  for (; !a.frames_set || k < a.frames; ++k) {
+    FrameSlot& s = slots[k % a.slots];
+    drain(s);  // frame k - slots: written before its slot is reused, so frames leave in order
+    try {
+      if (!y4m::read_frame(in, hd, static_cast<unsigned char*>(s.host_in))) break;
+    } catch (const srcnn::IOException& e) {
+      std::cout << "[ERROR] frame " << k << ": " << e.what() << std::endl;
+      rc = 1;
+      break;
+    }
+    srcnn::check(srcnn_memcpy_h2d(s.dev_in, s.host_in, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
+    p.super_resolve_yuv(s.src, s.dst, hd.w, hd.h, hd.cx, hd.cy, a.scale, hd.full_range, s.ws, ws_bytes,
+                        own_streams ? s.stream : nullptr);
+    s.busy = true;
+  }
+  for (unsigned i = 0; i < a.slots; ++i) drain(slots[(k + i) % a.slots]);  // the oldest first
+  if (store) {
+    out.flush();
+    if (!out) throw srcnn::IOException("cannot write '" + a.out + "'");
+  }
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::cout << "Frames: " << written << ", " << (sec > 0 ? double(written) / sec : 0.0) << " frames per second"
+            << (store ? ", saved to '" + a.out + "'" : std::string()) << std::endl;
+  p.context()->block();
+  return rc;
+}
+
+/** `cnn upscale`: the low-resolution image through srcnn_upscale, or a Y4M
+ * video through srcnn_upscale_yuv frame by frame */
 int upscale(ConfigBasedDataPipeline& p, const Args& a) {
+  {
+    std::ifstream in(a.in, std::ios::binary);
+    char magic[9] = {};
+    if (in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0) {
+      in.seekg(0);
+      return upscale_y4m(p, a, in);
+    }
+  }
+  if (a.frames_set || a.range >= 0 || a.slots_set)
+    throw std::runtime_error("--frames, --range and --slots need a Y4M input");
   ImageData img, res;
   srcnn::image::load(a.in, img, 4);
   p.super_resolve(img, a.scale, res);

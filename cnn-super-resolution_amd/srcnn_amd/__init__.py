@@ -43,6 +43,15 @@ class Net(ctypes.Structure):
 
 _NP = ctypes.POINTER(Net)
 
+
+class YuvFrame(ctypes.Structure):
+    """srcnn_yuv_frame: the device addresses of a frame's y, u and v planes and
+    the pitches in bytes of y and of u / v."""
+    _fields_ = [("y", _P), ("u", _P), ("v", _P), ("pitch_y", _U), ("pitch_c", _U)]
+
+
+_FP = ctypes.POINTER(YuvFrame)
+
 # name -> (restype, argtypes); int restype = status code checked by _call
 SIGNATURES = {
     "srcnn_abi_version": (_I, []),
@@ -52,6 +61,8 @@ SIGNATURES = {
     "srcnn_device_name": (_I, [ctypes.c_char_p, _S]),
     "srcnn_malloc": (_I, [ctypes.POINTER(_P), _S]),
     "srcnn_free": (_I, [_P]),
+    "srcnn_host_alloc": (_I, [ctypes.POINTER(_P), _S]),
+    "srcnn_host_free": (_I, [_P]),
     "srcnn_memcpy_h2d": (_I, [_P, _P, _S, _P]),
     "srcnn_memcpy_d2h": (_I, [_P, _P, _S, _P]),
     "srcnn_memcpy_d2d": (_I, [_P, _P, _S, _P]),
@@ -84,6 +95,9 @@ SIGNATURES = {
     "srcnn_swap_luma": (_I, [_P, _P, _P, _U, _U, _U, _U, _P]),
     "srcnn_upscale_luma": (_I, [_P, _P, _U, _U, _U, _U, _P]),
     "srcnn_upscale_compose": (_I, [_P, _P, _P, _U, _U, _U, _P]),
+    "srcnn_yuv_upscale_luma": (_I, [_P, _U, _P, _U, _U, _U, _U, _I, _P]),
+    "srcnn_upscale_planes_u8": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _P]),
+    "srcnn_yuv_compose_luma": (_I, [_P, _P, _U, _U, _U, _I, _P]),
     "srcnn_downscale_rgba": (_I, [_P, _P, _U, _U, _U, _P]),
     "srcnn_gather_tiles": (_I, [_P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _I, _P, _P, _P]),
     "srcnn_gather_batch": (_I, [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P]),
@@ -94,6 +108,8 @@ SIGNATURES = {
     "srcnn_quality": (_I, [_P, _I, _U, _P, _I, _U, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
+    "srcnn_upscale_yuv_workspace_bytes": (_S, [_NP, _U, _U, _U]),
+    "srcnn_upscale_yuv": (_I, [_NP, _FP, _FP, _U, _U, _U, _U, _U, _I, _P, _P, _S, _P]),
     "srcnn_evaluate_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_evaluate": (_I, [_NP, _P, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
@@ -149,6 +165,8 @@ OK, ERR_INVALID, ERR_HIP, ERR_WORKSPACE, ERR_ALLOC, ERR_COMM = 0, -1, -2, -3, -4
 COMM_ID_BYTES = 128
 # pixel formats of srcnn_quality (SRCNN_PIX_*)
 PIX_LUMA_F32, PIX_RGB8, PIX_RGBA8 = 1, 3, 4
+# range of a Y'CbCr frame's luma (SRCNN_YUV_*)
+YUV_LIMITED, YUV_FULL = 0, 1
 
 
 def _call(name, *args):
@@ -251,6 +269,17 @@ def event_destroy(e):
     _call("srcnn_event_destroy", e)
 
 
+def host_alloc(nbytes):
+    """Address of nbytes of page-locked host memory (srcnn_host_alloc)."""
+    p = _P()
+    _call("srcnn_host_alloc", ctypes.byref(p), nbytes)
+    return p.value or 0
+
+
+def host_free(p):
+    _call("srcnn_host_free", p)
+
+
 def memcpy_h2d(dst, src_addr, nbytes, s=None):
     _call("srcnn_memcpy_h2d", dst, src_addr, nbytes, s)
 
@@ -331,6 +360,27 @@ def upscale_compose(rgba, new_luma, rgb, w, h, scale, s=None):
     """bicubic x scale of the source's r, g, b + new_luma [scale*h][scale*w]
     -> rgb [scale*h][scale*w][3] u8 (srcnn_upscale_compose)."""
     _call("srcnn_upscale_compose", ptr(rgba), ptr(new_luma), ptr(rgb), w, h, scale, s)
+
+
+def yuv_upscale_luma(y, pitch_y, luma_padded, w, h, scale, pad, yuv_range, s=None):
+    """Y [h][w] u8 (rows pitch_y bytes apart) -> the bicubic x scale of its
+    luma (YUV_FULL: Y/255, YUV_LIMITED: (Y-16)/219), edge-replicated into the
+    padded plane [(scale*h+pad)][(scale*w+pad)] f32 (srcnn_yuv_upscale_luma)."""
+    _call("srcnn_yuv_upscale_luma", ptr(y), pitch_y, ptr(luma_padded), w, h, scale, pad, yuv_range, s)
+
+
+def upscale_planes_u8(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale, s=None):
+    """Two u8 planes [ph][pw] -> the top-left ow x oh of the bicubic x scale of
+    each, rounded to nearest and clamped, into two u8 planes
+    (srcnn_upscale_planes_u8)."""
+    _call("srcnn_upscale_planes_u8", ptr(src0), ptr(src1), src_pitch, pw, ph, ptr(dst0), ptr(dst1),
+          dst_pitch, ow, oh, scale, s)
+
+
+def yuv_compose_luma(luma, y, pitch_y, W, H, yuv_range, s=None):
+    """luma [H][W] f32 -> Y [H][W] u8, rows pitch_y bytes apart
+    (srcnn_yuv_compose_luma)."""
+    _call("srcnn_yuv_compose_luma", ptr(luma), ptr(y), pitch_y, W, H, yuv_range, s)
 
 
 def downscale_rgba(rgba, small, W, H, scale, s=None):
@@ -518,6 +568,24 @@ def upscale(net, rgba, w, h, scale, params, rgb, ws, ws_bytes, s=None):
     padded plane, forward, upscale_compose."""
     _call("srcnn_upscale", ctypes.byref(net), ptr(rgba), w, h, scale, ptr(params), ptr(rgb),
           ptr(ws), ws_bytes, s)
+
+
+def upscale_yuv_workspace_bytes(net, w, h, scale):
+    return _lib.srcnn_upscale_yuv_workspace_bytes(ctypes.byref(net), w, h, scale)
+
+
+def yuv_frame(y, u, v, pitch_y, pitch_c):
+    """A YuvFrame of three device planes (torch tensors or addresses)."""
+    return YuvFrame(ptr(y), ptr(u), ptr(v), pitch_y, pitch_c)
+
+
+def upscale_yuv(net, src, dst, w, h, cx, cy, scale, yuv_range, params, ws, ws_bytes, s=None):
+    """One planar Y'CbCr frame (src, a YuvFrame: w x h luma, chroma subsampled
+    by cx x cy) -> the frame scale times as large (dst) (srcnn_upscale_yuv):
+    yuv_upscale_luma, sub_mean over the padded plane, forward,
+    yuv_compose_luma, and upscale_planes_u8 for the chroma."""
+    _call("srcnn_upscale_yuv", ctypes.byref(net), ctypes.byref(src), ctypes.byref(dst), w, h, cx, cy,
+          scale, yuv_range, ptr(params), ptr(ws), ws_bytes, s)
 
 
 def evaluate_workspace_bytes(net, W, H, scale):

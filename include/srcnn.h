@@ -59,6 +59,10 @@ SRCNN_API int srcnn_set_device(int device);                 /* Context::init, Co
 SRCNN_API int srcnn_device_name(char* buf, size_t len);
 SRCNN_API int srcnn_malloc(void** ptr, size_t bytes);       /* Context::allocate, Context.cpp:164-176 */
 SRCNN_API int srcnn_free(void* ptr);                        /* RawMemoryHandle::release, Context.cpp:26-33 */
+/* page-locked host memory, which an asynchronous copy needs in order to be
+ * asynchronous (hipHostMalloc / hipHostFree; bytes == 0 gives NULL) */
+SRCNN_API int srcnn_host_alloc(void** ptr, size_t bytes);
+SRCNN_API int srcnn_host_free(void* ptr);
 /* blocking H2D / D2H (write_buffer / read_buffer with block=true, Context.cpp:235-290) */
 SRCNN_API int srcnn_memcpy_h2d(void* dst, const void* src, size_t bytes, srcnn_stream_t stream);
 SRCNN_API int srcnn_memcpy_d2h(void* dst, const void* src, size_t bytes, srcnn_stream_t stream);
@@ -203,6 +207,43 @@ SRCNN_API int srcnn_upscale_luma(const uint8_t* rgba, float* luma_padded, uint32
 SRCNN_API int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* rgb,
                                     uint32_t w, uint32_t h, uint32_t scale,
                                     srcnn_stream_t stream);
+
+/* The same front and back end for planar Y'CbCr frames with 8-bit samples
+ * (DESIGN.md 14 is the spec).  A plane is rows of bytes `pitch` bytes apart,
+ * pitch >= the row's width; the bytes between a row's end and the next row are
+ * never read and never written.  `range` selects how a Y byte maps to the
+ * net's luma v:
+ *   SRCNN_YUV_FULL     v = Y / 255            Y = rint(v * 255)
+ *   SRCNN_YUV_LIMITED  v = (Y - 16) / 219     Y = rint(v * 219 + 16)
+ * in fp32, Y clamped to [0, 255] after rounding to nearest, ties to even (not
+ * the truncation srcnn_swap_luma inherits from the reference).
+ *
+ * srcnn_yuv_upscale_luma: Y [h][w] u8 -> luma_padded [(H+pad)][(W+pad)] f32,
+ * srcnn_upscale_luma's plane (same resampling, same margins) of the luma v.
+ * With s = 1 and full range the interior is float(Y) / 255.0f bit for bit.
+ *
+ * srcnn_upscale_planes_u8: src0, src1 [ph][pw] u8 -> dst0, dst1 [oh][ow] u8:
+ * the top-left ow x oh of the bicubic x s of each plane, rounded to nearest
+ * (ties to even) and clamped to [0, 255]; s*(pw-1) < ow <= s*pw and
+ * s*(ph-1) < oh <= s*ph.  One call resamples a frame's two chroma planes; the
+ * crop is what odd luma sizes need.  With s = 1 the output
+ * is the source byte for byte.
+ *
+ * srcnn_yuv_compose_luma: luma [H][W] f32 (the net's output) -> Y [H][W] u8.
+ *
+ * SRCNN_ERR_INVALID: scale outside 1..4, a zero size, a pitch below the row's
+ * width, an unknown range, an output size outside the bounds above, a null
+ * buffer, or more than 2^31-1 elements in a plane. */
+enum { SRCNN_YUV_LIMITED = 0, SRCNN_YUV_FULL = 1 };
+SRCNN_API int srcnn_yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* luma_padded,
+                                     uint32_t w, uint32_t h, uint32_t scale, uint32_t pad,
+                                     int range, srcnn_stream_t stream);
+SRCNN_API int srcnn_upscale_planes_u8(const uint8_t* src0, const uint8_t* src1,
+                                      uint32_t src_pitch, uint32_t pw, uint32_t ph, uint8_t* dst0,
+                                      uint8_t* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
+                                      uint32_t scale, srcnn_stream_t stream);
+SRCNN_API int srcnn_yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W,
+                                     uint32_t H, int range, srcnn_stream_t stream);
 
 /* Training pairs from a full-size image, on the device (an MI355X extension;
  * the reference's pairs are made on the host, one file per sample).  The
@@ -372,8 +413,9 @@ typedef struct srcnn_net {
 } srcnn_net;
 
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
- * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale) launch
- * for this net, and the kernels of srcnn_make_pairs and srcnn_quality.
+ * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale,
+ * srcnn_upscale_yuv) launch for this net, and the kernels of srcnn_make_pairs
+ * and srcnn_quality.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -401,7 +443,8 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     extent of its outputs (grads: srcnn_net_param_count floats; sq_err: one
  *     float; params / momentum_bufs / params_out / mom_out likewise; out: the
  *     A3 extent; srcnn_train_activations: the three extents it documents;
- *     rgb: 3*W*H bytes; srcnn_make_pairs: count*tile*tile floats of X and of
+ *     rgb: 3*W*H bytes; srcnn_upscale_yuv: the row bytes of dst's three
+ *     planes, not the pitch gaps between them; srcnn_make_pairs: count*tile*tile floats of X and of
  *     T each; srcnn_gather_batch, which takes no workspace: n*tw*th floats of
  *     X and of T each and the n of means; srcnn_quality / srcnn_evaluate: the
  *     3 / 6 doubles of result);
@@ -459,6 +502,39 @@ SRCNN_API size_t srcnn_upscale_workspace_bytes(const srcnn_net* net, uint32_t w,
 SRCNN_API int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h,
                             uint32_t scale, const float* params, uint8_t* rgb, void* ws,
                             size_t ws_bytes, srcnn_stream_t stream);
+
+/* One planar Y'CbCr frame in, the super-resolved frame out, on the device.
+ * Only luma passes through the net; chroma is resampled as bytes.  The frame
+ * is w x h luma samples with chroma subsampled by (cx, cy) = (2, 2) for 4:2:0,
+ * (2, 1) for 4:2:2 or (1, 1) for 4:4:4: u and v are [ceil(h/cy)][ceil(w/cx)].
+ * The output frame is W x H = s*w x s*h with chroma [ceil(H/cy)][ceil(W/cx)].
+ * The call is
+ *   srcnn_yuv_upscale_luma(src->y, pad = f1+f2+f3-3) -> plane
+ *   srcnn_sub_mean over the whole padded plane (not added back, as in
+ *     srcnn_upscale)
+ *   srcnn_forward(plane) -> out [H][W]
+ *   srcnn_yuv_compose_luma(out -> dst->y)
+ *   srcnn_upscale_planes_u8(src->u, src->v -> dst->u, dst->v)
+ * and byte-identical to those calls; it works for every net srcnn_forward
+ * accepts; stream-ordered, no host synchronisation, no allocation.  `ws` holds
+ * the plane, the net output, the reduction scratch and the forward workspace
+ * (each 256-byte aligned) under the memory contract at
+ * srcnn_train_workspace_bytes; of dst it writes the W bytes of each Y row and
+ * the ceil(W/cx) bytes of each u and v row and nothing between the rows.
+ * srcnn_upscale_yuv_workspace_bytes returns 0 where the call would be invalid.
+ * Errors as the op-level calls, before any launch, plus SRCNN_ERR_INVALID for
+ * an invalid net or a subsampling other than the three and
+ * SRCNN_ERR_WORKSPACE for a workspace that is too small. */
+typedef struct srcnn_yuv_frame {
+  uint8_t *y, *u, *v;        /* device planes (of src only read) */
+  uint32_t pitch_y, pitch_c; /* bytes between rows of y, and of u and v */
+} srcnn_yuv_frame;
+SRCNN_API size_t srcnn_upscale_yuv_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                                   uint32_t scale);
+SRCNN_API int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src,
+                                const srcnn_yuv_frame* dst, uint32_t w, uint32_t h, uint32_t cx,
+                                uint32_t cy, uint32_t scale, int range, const float* params,
+                                void* ws, size_t ws_bytes, srcnn_stream_t stream);
 
 /* "How many dB over bicubic?" in one call: the full-size ground truth rgba
  * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at

@@ -1,0 +1,58 @@
+"""The Y4M reader under AddressSanitizer + UndefinedBehaviorSanitizer (CPU).
+
+`cnn upscale -i VIDEO.y4m` reads a user's file.  host/test/y4m_fuzz.cpp is a
+stand-alone deterministic mutation fuzzer with its own main: it is compiled
+here together with Y4m.cpp (and the image codecs, for image::check_dims) with
+g++ -fsanitize=address,undefined -fno-sanitize-recover=all and run directly
+over generated seed streams; it mutates header bytes, header fields and the
+file's length.  Every mutation must read to its end or raise; a crash or a
+sanitizer report fails the test."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+HOST = os.path.join(ROOT, "cnn-super-resolution_amd", "host")
+
+
+def _seeds(d):
+    rng = np.random.default_rng(5)
+    out = []
+    for name, head, (w, h, cw, ch) in (
+            ("a420.y4m", "YUV4MPEG2 W37 H23 F30:1 Ip A1:1 C420jpeg XYSCSS=420JPEG", (37, 23, 19, 12)),
+            ("b422.y4m", "YUV4MPEG2 W18 H7 F25:1 Ip C422 XCOLORRANGE=FULL", (18, 7, 9, 7)),
+            ("c444.y4m", "YUV4MPEG2 W5 H3", (5, 3, 3, 2))):
+        p = os.path.join(d, name)
+        with open(p, "wb") as fh:
+            fh.write(head.encode() + b"\n")
+            for k in range(3):
+                fh.write(b"FRAME Ip\n" if k == 1 else b"FRAME\n")
+                fh.write(rng.integers(0, 256, w * h + 2 * cw * ch, dtype=np.uint8).tobytes())
+        out.append(p)
+    return out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_y4m_reader_under_asan_ubsan(tmp_path):
+    exe = str(tmp_path / "y4m_fuzz")
+    src = [os.path.join(HOST, "test", "y4m_fuzz.cpp")] + [os.path.join(HOST, "src", f)
+                                                         for f in ("Y4m.cpp", "Image.cpp", "Jpeg.cpp")]
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),
+                        "-I" + os.path.join(HOST, "src")] + src + ["-o", exe, "-lz"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    seeds = _seeds(str(tmp_path))
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, "--iters", "400"] + seeds, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if "mutations=" in l]
+    assert len(lines) == len(seeds)  # 3 x 400 = 1200 mutations
+    # the mutations exercise both outcomes
+    ok = sum(int(l.split("read=")[1].split()[0]) for l in lines)
+    rej = sum(int(l.split("rejected=")[1].split()[0]) for l in lines)
+    assert ok > 100 and rej > 300, lines
