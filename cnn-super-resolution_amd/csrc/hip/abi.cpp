@@ -96,25 +96,44 @@ int up_dims(const char* who, uint32_t w, uint32_t h, uint32_t scale, uint32_t pa
 
 // srcnn_yuv_* / srcnn_upscale_planes_u8: the sizes of one byte plane and of
 // its resampled counterpart against what the kernels of yuv.hip can index (int
-// coordinates, at most 2^31-1 elements in a plane; row offsets are size_t)
-int plane_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch) {
+// coordinates, at most 2^31-1 elements in a plane; row offsets are size_t).
+// A pixel is nch samples of B bytes: the pitch is in bytes, and
+// even for two-byte samples.
+int plane_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch, uint32_t B = 1,
+               uint32_t nch = 1) {
   SRCNN_REQUIRE(w > 0 && h > 0, "%s: empty plane %ux%u", who, w, h);
-  SRCNN_REQUIRE(pitch >= w, "%s: pitch %u is below the row width %u", who, pitch, w);
-  SRCNN_REQUIRE((uint64_t)w * h <= 0x7fffffffull,
+  if (B * nch == 1) {
+    SRCNN_REQUIRE(pitch >= w, "%s: pitch %u is below the row width %u", who, pitch, w);
+  } else {
+    SRCNN_REQUIRE(pitch >= (uint64_t)w * nch * B,
+                  "%s: pitch %u is below the %llu bytes of a row of %u x %u samples of %u bytes", who,
+                  pitch, (unsigned long long)w * nch * B, w, nch, B);
+  }
+  SRCNN_REQUIRE(B == 1 || pitch % 2 == 0, "%s: pitch %u of two-byte samples is odd", who, pitch);
+  SRCNN_REQUIRE((uint64_t)w * h * nch <= 0x7fffffffull,
                 "%s: plane %ux%u exceeds the kernels' 32-bit index: a plane's elements must "
                 "number at most 2^31-1",
                 who, w, h);
   return SRCNN_OK;
 }
+// the sample format of DESIGN.md 15; *B: bytes per sample
+int yuv_samples(const char* who, uint32_t bits, uint32_t msb, uint32_t* B) {
+  SRCNN_REQUIRE(bits >= 8 && bits <= 16, "%s: %u bits per sample is outside 8..16", who, bits);
+  SRCNN_REQUIRE(msb <= 1, "%s: msb %u is neither 0 nor 1", who, msb);
+  SRCNN_REQUIRE(!(msb && bits == 8), "%s: msb 1 with one-byte samples", who);
+  *B = bits == 8 ? 1 : 2;
+  return SRCNN_OK;
+}
+bool odd_address(uint32_t B, const void* p) { return B == 2 && ((uintptr_t)p & 1); }
 int yuv_range(const char* who, int range) {
   SRCNN_REQUIRE(range == SRCNN_YUV_LIMITED || range == SRCNN_YUV_FULL,
                 "%s: range %d is neither SRCNN_YUV_LIMITED nor SRCNN_YUV_FULL", who, range);
   return SRCNN_OK;
 }
 int yuv_luma_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch, uint32_t scale,
-                  uint32_t pad, UpDims* d) {
+                  uint32_t pad, UpDims* d, uint32_t B = 1) {
   SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
-  if (int rc = plane_dims(who, w, h, pitch)) return rc;
+  if (int rc = plane_dims(who, w, h, pitch, B)) return rc;
   const uint64_t lim = 0x7fffffffull;
   const uint64_t W = (uint64_t)w * scale, H = (uint64_t)h * scale;
   SRCNN_REQUIRE(W + pad <= lim && H + pad <= lim && (W + pad) * (H + pad) <= lim,
@@ -128,10 +147,10 @@ int yuv_luma_dims(const char* who, uint32_t w, uint32_t h, uint32_t pitch, uint3
   return SRCNN_OK;
 }
 int planes_dims(const char* who, uint32_t src_pitch, uint32_t pw, uint32_t ph, uint32_t dst_pitch,
-                uint32_t ow, uint32_t oh, uint32_t scale) {
+                uint32_t ow, uint32_t oh, uint32_t scale, uint32_t B = 1, uint32_t nch = 1) {
   SRCNN_REQUIRE(scale >= 1 && scale <= 4, "%s: scale %u is not 1, 2, 3 or 4", who, scale);
-  if (int rc = plane_dims(who, pw, ph, src_pitch)) return rc;
-  if (int rc = plane_dims(who, ow, oh, dst_pitch)) return rc;
+  if (int rc = plane_dims(who, pw, ph, src_pitch, B, nch)) return rc;
+  if (int rc = plane_dims(who, ow, oh, dst_pitch, B, nch)) return rc;
   const uint64_t s = scale;
   SRCNN_REQUIRE(s * (pw - 1) < ow && ow <= s * pw && s * (ph - 1) < oh && oh <= s * ph,
                 "%s: output %ux%u is not a crop of the x%u of %ux%u that keeps its last tile", who,
@@ -441,6 +460,58 @@ int srcnn_yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint
   SRCNN_REQUIRE(luma && y, "yuv_compose_luma: null buffer");
   return srcnn::yuv_compose_luma(luma, y, pitch_y, W, H, range == SRCNN_YUV_FULL,
                                  as_stream(stream));
+}
+
+int srcnn_yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
+                             uint32_t h, uint32_t scale, uint32_t pad, uint32_t bits, uint32_t msb,
+                             int range, srcnn_stream_t stream) {
+  UpDims d;
+  uint32_t B;
+  if (int rc = yuv_samples("yuv_upscale_luma16", bits, msb, &B)) return rc;
+  if (int rc = yuv_luma_dims("yuv_upscale_luma16", w, h, pitch_y, scale, pad, &d, B)) return rc;
+  if (int rc = yuv_range("yuv_upscale_luma16", range)) return rc;
+  SRCNN_REQUIRE(y && luma_padded, "yuv_upscale_luma16: null buffer");
+  SRCNN_REQUIRE(!odd_address(B, y), "yuv_upscale_luma16: odd address of two-byte samples");
+  return srcnn::yuv_upscale_luma16(y, pitch_y, luma_padded, w, h, scale, pad, bits, msb != 0,
+                                   range == SRCNN_YUV_FULL, as_stream(stream));
+}
+
+int srcnn_yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                             uint32_t bits, uint32_t msb, int range, srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples("yuv_compose_luma16", bits, msb, &B)) return rc;
+  if (int rc = plane_dims("yuv_compose_luma16", W, H, pitch_y, B)) return rc;
+  if (int rc = yuv_range("yuv_compose_luma16", range)) return rc;
+  SRCNN_REQUIRE(luma && y, "yuv_compose_luma16: null buffer");
+  SRCNN_REQUIRE(!odd_address(B, y), "yuv_compose_luma16: odd address of two-byte samples");
+  return srcnn::yuv_compose_luma16(luma, y, pitch_y, W, H, bits, msb != 0, range == SRCNN_YUV_FULL,
+                                   as_stream(stream));
+}
+
+int srcnn_upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
+                         uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow,
+                         uint32_t oh, uint32_t scale, uint32_t bits, uint32_t msb, uint32_t layout,
+                         srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples("upscale_planes", bits, msb, &B)) return rc;
+  SRCNN_REQUIRE(layout == SRCNN_YUV_PLANAR || layout == SRCNN_YUV_SEMIPLANAR,
+                "upscale_planes: layout %u is neither SRCNN_YUV_PLANAR nor SRCNN_YUV_SEMIPLANAR",
+                layout);
+  const bool semi = layout == SRCNN_YUV_SEMIPLANAR;
+  if (int rc = planes_dims("upscale_planes", src_pitch, pw, ph, dst_pitch, ow, oh, scale, B,
+                           semi ? 2 : 1))
+    return rc;
+  SRCNN_REQUIRE(src0 && dst0, "upscale_planes: null buffer");
+  if (semi) {
+    SRCNN_REQUIRE(!src1 && !dst1, "upscale_planes: a semi-planar frame has no second chroma plane");
+  } else {
+    SRCNN_REQUIRE(src1 && dst1, "upscale_planes: null buffer");
+  }
+  SRCNN_REQUIRE(!odd_address(B, src0) && !odd_address(B, src1) && !odd_address(B, dst0) &&
+                    !odd_address(B, dst1),
+                "upscale_planes: odd address of two-byte samples");
+  return srcnn::upscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
+                               bits, msb != 0, semi, as_stream(stream));
 }
 
 int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
@@ -924,19 +995,19 @@ struct YuvDims {
   UpDims d;
   uint32_t pad, cw, ch, CW, CH;
 };
-static int yuv_dims(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t cx, uint32_t cy,
-                    uint32_t scale, YuvDims* y) {
-  SRCNN_REQUIRE(net, "upscale_yuv: null srcnn_net");
+static int yuv_dims(const char* who, const srcnn_net* net, uint32_t w, uint32_t h, uint32_t cx,
+                    uint32_t cy, uint32_t scale, YuvDims* y) {
+  SRCNN_REQUIRE(net, "%s: null srcnn_net", who);
   size_t off[6];
   if (int rc = srcnn_net_offsets(net, off)) return rc;
   const uint64_t pad64 = (uint64_t)net->f1 + net->f2 + net->f3 - 3;
-  SRCNN_REQUIRE(pad64 <= 0x7fffffffull, "upscale_yuv: total padding %llu too large",
+  SRCNN_REQUIRE(pad64 <= 0x7fffffffull, "%s: total padding %llu too large", who,
                 (unsigned long long)pad64);
   y->pad = (uint32_t)pad64;
   SRCNN_REQUIRE((cx == 2 && cy == 2) || (cx == 2 && cy == 1) || (cx == 1 && cy == 1),
-                "upscale_yuv: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)",
+                "%s: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)", who,
                 cx, cy);
-  if (int rc = yuv_luma_dims("upscale_yuv", w, h, w, scale, y->pad, &y->d)) return rc;
+  if (int rc = yuv_luma_dims(who, w, h, w, scale, y->pad, &y->d)) return rc;
   y->cw = (w - 1) / cx + 1;
   y->ch = (h - 1) / cy + 1;
   y->CW = (y->d.W - 1) / cx + 1;
@@ -948,7 +1019,7 @@ size_t srcnn_upscale_yuv_workspace_bytes(const srcnn_net* net, uint32_t w, uint3
                                          uint32_t scale) {
   YuvDims y;
   UpWs L;
-  if (yuv_dims(net, w, h, 1, 1, scale, &y)) return 0;
+  if (yuv_dims("upscale_yuv", net, w, h, 1, 1, scale, &y)) return 0;
   return up_ws(net, y.d, &L) ? L.total : 0;
 }
 
@@ -956,7 +1027,7 @@ int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src, const sr
                       uint32_t w, uint32_t h, uint32_t cx, uint32_t cy, uint32_t scale, int range,
                       const float* params, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
   YuvDims y;
-  if (int rc = yuv_dims(net, w, h, cx, cy, scale, &y)) return rc;
+  if (int rc = yuv_dims("upscale_yuv", net, w, h, cx, cy, scale, &y)) return rc;
   if (int rc = yuv_range("upscale_yuv", range)) return rc;
   SRCNN_REQUIRE(src && dst && params && ws, "upscale_yuv: null buffer");
   SRCNN_REQUIRE(src->y && src->u && src->v && dst->y && dst->u && dst->v,
@@ -984,6 +1055,60 @@ int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src, const sr
   if ((rc = srcnn_yuv_compose_luma(out, dst->y, dst->pitch_y, d.W, d.H, range, stream))) return rc;
   return srcnn_upscale_planes_u8(src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v,
                                  dst->pitch_c, y.CW, y.CH, scale, stream);
+}
+
+int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                        const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst, uint32_t w,
+                        uint32_t h, uint32_t scale, const float* params, void* ws, size_t ws_bytes,
+                        srcnn_stream_t stream) {
+  SRCNN_REQUIRE(fmt, "upscale_frame: null srcnn_yuv_format");
+  YuvDims y;
+  uint32_t B;
+  if (int rc = yuv_dims("upscale_frame", net, w, h, fmt->cx, fmt->cy, scale, &y)) return rc;
+  if (int rc = yuv_range("upscale_frame", fmt->range)) return rc;
+  if (int rc = yuv_samples("upscale_frame", fmt->bits, fmt->msb, &B)) return rc;
+  SRCNN_REQUIRE(fmt->layout == SRCNN_YUV_PLANAR || fmt->layout == SRCNN_YUV_SEMIPLANAR,
+                "upscale_frame: layout %u is neither SRCNN_YUV_PLANAR nor SRCNN_YUV_SEMIPLANAR",
+                fmt->layout);
+  const bool semi = fmt->layout == SRCNN_YUV_SEMIPLANAR;
+  SRCNN_REQUIRE(src && dst && params && ws, "upscale_frame: null buffer");
+  SRCNN_REQUIRE(src->y && src->u && dst->y && dst->u, "upscale_frame: null plane");
+  if (semi) {
+    SRCNN_REQUIRE(!src->v && !dst->v, "upscale_frame: a semi-planar frame has no v plane");
+  } else {
+    SRCNN_REQUIRE(src->v && dst->v, "upscale_frame: null plane");
+  }
+  SRCNN_REQUIRE(!odd_address(B, src->y) && !odd_address(B, src->u) && !odd_address(B, src->v) &&
+                    !odd_address(B, dst->y) && !odd_address(B, dst->u) && !odd_address(B, dst->v),
+                "upscale_frame: odd address of two-byte samples");
+  // (the sizes again, now with the frames' pitches)
+  UpDims d;
+  if (int rc = yuv_luma_dims("upscale_frame", w, h, src->pitch_y, scale, y.pad, &d, B)) return rc;
+  if (int rc = plane_dims("upscale_frame", d.W, d.H, dst->pitch_y, B)) return rc;
+  if (int rc = planes_dims("upscale_frame", src->pitch_c, y.cw, y.ch, dst->pitch_c, y.CW, y.CH,
+                           scale, B, semi ? 2 : 1))
+    return rc;
+  UpWs L;
+  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "upscale_frame: workspace %zu B < %zu B", ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  float* out = reinterpret_cast<float*>(p + L.out);
+  int rc;
+  if ((rc = srcnn_yuv_upscale_luma16(src->y, src->pitch_y, plane, w, h, scale, y.pad, fmt->bits,
+                                     fmt->msb, fmt->range, stream)))
+    return rc;
+  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
+    return rc;
+  if ((rc = srcnn_yuv_compose_luma16(out, dst->y, dst->pitch_y, d.W, d.H, fmt->bits, fmt->msb,
+                                     fmt->range, stream)))
+    return rc;
+  return srcnn_upscale_planes(src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v,
+                              dst->pitch_c, y.CW, y.CH, scale, fmt->bits, fmt->msb, fmt->layout,
+                              stream);
 }
 
 // regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |

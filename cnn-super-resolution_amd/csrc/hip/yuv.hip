@@ -1,17 +1,22 @@
-// yuv.hip -- the device front and back end of srcnn_upscale_yuv:
-//   yuv_upscale_luma   Y [h][w] u8 (pitched) -> bicubic x S of the normalised
+// yuv.hip -- the device front and back end of srcnn_upscale_yuv
+// and of srcnn_upscale_frame:
+//   yuv_upscale_luma   Y [h][w] (pitched) -> bicubic x S of the normalised
 //                      luma, edge-replicated into the padded plane
 //                      [(S*h+P)][(S*w+P)] f32 the net reads
-//   upscale_planes_u8  two u8 planes [ph][pw] (pitched) -> bicubic x S, rounded
-//                      to nearest and clamped, the top-left ow x oh of each
-//                      into two u8 planes (pitched): a frame's chroma
-//   yuv_compose_luma   the net's luma [H][W] f32 -> Y [H][W] u8 (pitched)
+//   upscale_planes     a frame's chroma, [ph][pw] (pitched), as two planes or
+//                      as one plane of (U, V) pairs -> bicubic x S, rounded to
+//                      nearest and clamped, the top-left ow x oh in the same
+//                      layout (pitched)
+//   yuv_compose_luma   the net's luma [H][W] f32 -> Y [H][W] (pitched)
+// A sample is one byte, or a 16-bit word that holds 9 to 16 bits in its low or
+// in its high bits (template parameter B: bytes per sample; struct Fmt).
 // The resampling is upscale.hip's (bicubic.hpp holds what the
 // two files share): one workgroup per tile of JX x JY source pixels, the
 // source patch staged in LDS as floats, a horizontal pass into LDS, a vertical
-// pass into registers.  The source here is one byte per pixel at an arbitrary
-// pitch, so the patch is fetched in aligned 4-byte words wherever a word lies
-// inside the row, and in clamped single bytes at the image's edges.
+// pass into registers.  The source here is one or two bytes per sample at an
+// arbitrary pitch, so the patch is fetched in aligned words of four samples
+// wherever a word lies inside the row, and in clamped single samples at the
+// image's edges.
 #include "bicubic.hpp"
 #include "common.hpp"
 #include "ops.hpp"
@@ -19,50 +24,104 @@
 namespace srcnn {
 namespace {
 
-// clamped fetch of the tile's source patch from a byte plane: lane (r, k)
-// takes the k-th 4-byte-aligned word under patch row r
-template <typename T, typename Store>
-__device__ __forceinline__ void stage_bytes(const uint8_t* __restrict__ src, size_t pitch, int w,
-                                            int h, int j0, int i0, Store store) {
-  constexpr int NW = (T::PC + 6) / 4;  // words under PC bytes at a skew of up to 3
-  const int xs = j0 - 2;               // the column of patch column 0
+template <int B>
+struct Sample {
+  using type = uint8_t;
+};
+template <>
+struct Sample<2> {
+  using type = uint16_t;
+};
+
+// How a two-byte sample sits in its word: the value is word >> sh (sh = 0: in
+// the low bits, nothing masked; sh = 16 - bits: in the high bits) and at most
+// maxv = 2^bits - 1 when written.  A one-byte sample is the byte, at most 255.
+template <int B>
+struct Fmt {
+  __device__ __forceinline__ uint32_t value(uint32_t word) const { return word; }
+};
+template <>
+struct Fmt<2> {
+  int sh;
+  float maxv;
+  __device__ __forceinline__ uint32_t value(uint32_t word) const { return word >> sh; }
+};
+
+// clamped fetch of the tile's source patch from a plane of B-byte samples, NCH
+// of them interleaved per pixel: lane (r, k) takes the k-th aligned word of
+// four samples (4 bytes, or 8 of two-byte samples) under patch row r;
+// store(r, c, ch, word) receives the sample's word of channel ch of patch
+// column c.  A word is loaded whole only where it lies inside the row's
+// w * NCH * B bytes, else its samples singly with clamped indices: no load
+// leaves the row.
+template <typename T, int B, int NCH, typename Store>
+__device__ __forceinline__ void stage_samples(const uint8_t* __restrict__ src, size_t pitch, int w,
+                                              int h, int j0, int i0, Store store) {
+  using E = typename Sample<B>::type;
+  constexpr int EW = 4;                       // samples in a word
+  constexpr int PE = T::PC * NCH;             // samples under a patch row
+  constexpr int NW = (PE + 2 * EW - 2) / EW;  // words under them at a skew of up to EW - 1
+  constexpr uint32_t mask = B == 1 ? 255u : 65535u;
+  const int ne = w * NCH;         // samples in a row
+  const int xs = (j0 - 2) * NCH;  // the sample of patch column 0, channel 0
   for (int it = threadIdx.x; it < T::PR * NW; it += kThreads) {
     const int r = it / NW, k = it - r * NW;
     const int sy = min(max(i0 - 2 + r, 0), h - 1);
     const uint8_t* row = src + (size_t)sy * pitch;
-    const int skew = (int)(((uintptr_t)row + (uintptr_t)(intptr_t)xs) & 3);
-    const int c0 = 4 * k - skew;  // patch column of the word's first byte
-    const int x0 = xs + c0;       // its column: row + x0 is 4-byte aligned
-    if (x0 >= 0 && x0 + 3 < w) {
-      const uint32_t v = *reinterpret_cast<const uint32_t*>(row + x0);
+    const int skew = (int)(((uintptr_t)row + (uintptr_t)((intptr_t)xs * B)) & (EW * B - 1)) / B;
+    const int c0 = EW * k - skew;  // patch sample of the word's first sample
+    const int x0 = xs + c0;        // its index in the row: row + x0 * B is aligned to the word
+    if (x0 >= 0 && x0 + EW - 1 < ne) {
+      uint32_t v[B];
+      if constexpr (B == 1) {
+        v[0] = *reinterpret_cast<const uint32_t*>(row + x0);
+      } else {
+        const uint2 t = *reinterpret_cast<const uint2*>(row + (size_t)x0 * B);
+        v[0] = t.x;
+        v[1] = t.y;
+      }
 #pragma unroll
-      for (int b = 0; b < 4; b++)
-        if (c0 + b >= 0 && c0 + b < T::PC) store(r, c0 + b, (float)((v >> (8 * b)) & 255u));
+      for (int b = 0; b < EW; b++)
+        if (c0 + b >= 0 && c0 + b < PE)
+          store(r, (int)((unsigned)(c0 + b) / NCH), (int)((unsigned)(c0 + b) % NCH),
+                (v[b * B / 4] >> (8 * B * b % 32)) & mask);
     } else {
 #pragma unroll
-      for (int b = 0; b < 4; b++)
-        if (c0 + b >= 0 && c0 + b < T::PC) store(r, c0 + b, (float)row[min(max(x0 + b, 0), w - 1)]);
+      for (int b = 0; b < EW; b++)
+        if (c0 + b >= 0 && c0 + b < PE) {
+          // the pixel is clamped, the channel kept (x0 + b may be negative)
+          const int e = x0 + b;
+          const int ec = NCH == 1 ? min(max(e, 0), w - 1) : min(max(e >> 1, 0), w - 1) * 2 + (e & 1);
+          store(r, (int)((unsigned)(c0 + b) / NCH), (int)((unsigned)(c0 + b) % NCH),
+                (uint32_t) reinterpret_cast<const E*>(row)[ec]);
+        }
     }
   }
 }
 
-// the normalised luma of a Y byte: (Y - off) / div with (off, div) = (0, 255)
-// for full range and (16, 219) for limited; a true division, never contracted,
-// so that scale 1 at full range gives float(Y) / 255.0f bit for bit
+// the normalised luma of a Y sample: (Y - off) / div with (off, div) = (0, 255)
+// for full range and (16, 219) for limited at 8 bits, both times 2^(bits-8)
+// (full range: 2^bits - 1) above; a true division, never contracted, so that
+// scale 1 at full range gives float(Y) / float(2^bits - 1) bit for bit
 __device__ __forceinline__ float luma_of_y(float y, float off, float div) {
 #pragma clang fp contract(off)
   return (y - off) / div;
 }
 
-// clamp(rintf(v), 0, 255) as a byte (rintf: round to nearest, ties to even)
-__device__ __forceinline__ uint32_t quantise(float v) {
-  return (uint32_t)fminf(fmaxf(rintf(v), 0.0f), 255.0f);
+// clamp(rintf(v), 0, 2^bits - 1) as the sample's word (rintf: round to
+// nearest, ties to even)
+template <int B>
+__device__ __forceinline__ uint32_t quantise(float v, Fmt<B> f) {
+  if constexpr (B == 1)
+    return (uint32_t)fminf(fmaxf(rintf(v), 0.0f), 255.0f);
+  else
+    return (uint32_t)fminf(fmaxf(rintf(v), 0.0f), f.maxv) << f.sh;
 }
 
-template <int S>
+template <int S, int B>
 __global__ __launch_bounds__(kThreads) void yuv_upscale_luma_kernel(
     const uint8_t* __restrict__ y, size_t pitch, float* __restrict__ out, int w, int h, int P,
-    int tiles_x, float off, float div) {
+    int tiles_x, float off, float div, Fmt<B> f) {
   using T = Tile<S, false>;
   __shared__ float s_src[T::PR][T::PCP];
   __shared__ float s_h[T::PR][T::TX + 1];
@@ -70,8 +129,9 @@ __global__ __launch_bounds__(kThreads) void yuv_upscale_luma_kernel(
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int j0 = tx * T::JX, i0 = ty * T::JY;
 
-  stage_bytes<T>(y, pitch, w, h, j0, i0,
-                 [&](int r, int c, float v) { s_src[r][c] = luma_of_y(v, off, div); });
+  stage_samples<T, B, 1>(y, pitch, w, h, j0, i0, [&](int r, int c, int, uint32_t v) {
+    s_src[r][c] = luma_of_y((float)f.value(v), off, div);
+  });
   __syncthreads();
   hpass<S, T, 1>([&](int r, int c, int) { return s_src[r][c]; },
                  [&](int, int r, int x, float v) { s_h[r][x] = v; });
@@ -80,44 +140,50 @@ __global__ __launch_bounds__(kThreads) void yuv_upscale_luma_kernel(
   store_plane_tile<S>(s_h, out, w, h, P, tx, ty, i0, tiles_x, tiles_y);
 }
 
-// blockIdx.y selects the plane.  The tile is upscale_compose's (64 x 8 source
-// pixels at S <= 2, else 32 x 16): an output row of the tile is 64 - 128 bytes.
-template <int S>
-__global__ __launch_bounds__(kThreads) void upscale_planes_u8_kernel(
+// NCH = 1: two planes, blockIdx.y selects one.  NCH = 2: src0 / dst0 hold
+// (U, V) pairs, the two channels of one pass; pw, ow and the tile count pairs.
+// The tile is upscale_compose's (64 x 8 source pixels at S <= 2, else 32 x 16):
+// an output row of the tile is 64 - 512 bytes.
+template <int S, int B, int NCH>
+__global__ __launch_bounds__(kThreads) void upscale_planes_kernel(
     const uint8_t* __restrict__ src0, const uint8_t* __restrict__ src1, size_t src_pitch, int pw,
     int ph, uint8_t* __restrict__ dst0, uint8_t* __restrict__ dst1, size_t dst_pitch, int ow, int oh,
-    int tiles_x) {
+    int tiles_x, Fmt<B> f) {
   using T = Tile<S, true>;
+  using E = typename Sample<B>::type;
   constexpr int TX = T::TX, TY = T::TY;
-  constexpr int RB = kThreads / 32;  // output rows per batch
-  constexpr int STG = 16 + TX;       // staged row: up to 15 bytes of skew + the pixels
-  __shared__ float s_src[T::PR][T::PCP];
-  __shared__ float s_h[T::PR][TX + 1];
+  constexpr int RB = kThreads / 32;        // output rows per batch
+  constexpr int STG = 16 + TX * NCH * B;   // staged row: up to 15 bytes of skew + the samples
+  __shared__ float s_src[NCH][T::PR][T::PCP];
+  __shared__ float s_h[NCH][T::PR][TX + 1];
   __shared__ __attribute__((aligned(16))) uint8_t s_out[RB][STG];
-  const uint8_t* __restrict__ src = blockIdx.y ? src1 : src0;
-  uint8_t* __restrict__ dst = blockIdx.y ? dst1 : dst0;
+  const uint8_t* __restrict__ src = NCH == 1 && blockIdx.y ? src1 : src0;
+  uint8_t* __restrict__ dst = NCH == 1 && blockIdx.y ? dst1 : dst0;
   const int tid = threadIdx.x;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int j0 = tx * T::JX, i0 = ty * T::JY;
 
-  stage_bytes<T>(src, src_pitch, pw, ph, j0, i0, [&](int r, int c, float v) { s_src[r][c] = v; });
+  stage_samples<T, B, NCH>(src, src_pitch, pw, ph, j0, i0, [&](int r, int c, int ch, uint32_t v) {
+    s_src[ch][r][c] = (float)f.value(v);
+  });
   __syncthreads();
-  hpass<S, T, 1>([&](int r, int c, int) { return s_src[r][c]; },
-                 [&](int, int r, int x, float v) { s_h[r][x] = v; });
+  hpass<S, T, NCH>([&](int r, int c, int ch) { return s_src[ch][r][c]; },
+                   [&](int ch, int r, int x, float v) { s_h[ch][r][x] = v; });
   __syncthreads();
 
   // the tile's share of the ow x oh output: the last tile of a row or column
   // is cut by the plane (S*pw x S*ph) or by the crop, whichever is smaller
   const int X0 = tx * TX, Y0 = ty * TY;
-  const int ncol = min(TX, ow - X0), nrow = min(TY, oh - Y0);  // bytes of a row; rows
+  const int ncol = min(TX, ow - X0), nrow = min(TY, oh - Y0);  // pixels of a row; rows
+  const int nb = ncol * (NCH * B);                             // bytes of a row
   const int c5 = tid & 31, rr = tid >> 5;
   for (int yb = 0; yb < nrow; yb += RB) {
     const bool live = yb + rr < nrow;
     const int Y = Y0 + yb + rr;
-    uint8_t* grow = dst + (size_t)Y * dst_pitch + X0;
+    uint8_t* gbytes = dst + (size_t)Y * dst_pitch + (size_t)X0 * (NCH * B);
     // the row is staged in LDS at the skew its global address has, so that
     // 16-byte chunks of the two line up
-    const int o = (int)((uintptr_t)grow & 15);
+    const int o = (int)((uintptr_t)gbytes & 15);
     if (live) {
       const int jy = Y / S, ky = Y - jy * S;
       const int rb = jy - i0 + tap_base(S, ky) + 1;
@@ -127,22 +193,31 @@ __global__ __launch_bounds__(kThreads) void upscale_planes_u8_kernel(
 #pragma unroll
       for (int i = 0; i < TX / 32; i++) {
         const int cx = c5 + 32 * i;
-        if (cx < ncol)
-          s_out[rr][o + cx] = (uint8_t)quantise(w0 * s_h[rb][cx] + w1 * s_h[rb + 1][cx] +
-                                                w2 * s_h[rb + 2][cx] + w3 * s_h[rb + 3][cx]);
+        if (cx < ncol) {
+#pragma unroll
+          for (int ch = 0; ch < NCH; ch++)
+            *reinterpret_cast<E*>(&s_out[rr][o + (cx * NCH + ch) * B]) =
+                (E)quantise<B>(w0 * s_h[ch][rb][cx] + w1 * s_h[ch][rb + 1][cx] +
+                                   w2 * s_h[ch][rb + 2][cx] + w3 * s_h[ch][rb + 3][cx],
+                               f);
+        }
       }
     }
     __syncthreads();
     if (live) {
-      // bytes up to the first 16-byte boundary, 16-byte chunks, the rest
-      const int head = min((16 - o) & 15, ncol);
-      if (c5 < head) grow[c5] = s_out[rr][o + c5];
-      const int nch = (ncol - head) >> 4;  // <= TX/16 <= 8 of the row's 32 lanes
+      // samples up to the first 16-byte boundary, 16-byte chunks, the rest
+      // (in bytes: o, nb and head are multiples of B)
+      auto copy = [&](int at) {
+        *reinterpret_cast<E*>(gbytes + at) = *reinterpret_cast<const E*>(&s_out[rr][o + at]);
+      };
+      const int head = min((16 - o) & 15, nb);
+      if (c5 * B < head) copy(c5 * B);
+      const int nch = (nb - head) >> 4;  // <= TX*NCH*B/16 <= 32, the row's lanes
       if (c5 < nch)
-        *reinterpret_cast<uint4*>(grow + head + 16 * c5) =
+        *reinterpret_cast<uint4*>(gbytes + head + 16 * c5) =
             *reinterpret_cast<const uint4*>(&s_out[rr][o + head + 16 * c5]);
-      const int t = head + 16 * nch + c5;
-      if (t < ncol) grow[t] = s_out[rr][o + t];
+      const int t = head + 16 * nch + c5 * B;  // fewer than 16 bytes are left
+      if (t < nb) copy(t);
     }
     __syncthreads();
   }
@@ -153,46 +228,64 @@ __global__ __launch_bounds__(kThreads) void upscale_planes_u8_kernel(
 // 16-byte boundary, so the loads are 16 bytes wide but not 16-byte aligned
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
 
-// One wavefront per row, four rows per workgroup.  A lane takes 16 pixels:
-// four 16-byte loads, one 16-byte store; the bytes before the row's first
-// 16-byte boundary and after its last go one per lane.
+// One-byte samples: one wavefront per row, four rows per workgroup.  A lane
+// takes the 16 / B pixels of one 16-byte store: 16-byte loads, one 16-byte
+// store; the samples before the row's first 16-byte boundary and after its
+// last go one per lane.  Two-byte samples: the four wavefronts of a workgroup
+// share one row, so that twice the output bytes leave in as many passes per
+// lane as with bytes.
+template <int B>
 __global__ __launch_bounds__(kThreads) void yuv_compose_luma_kernel(
     const float* __restrict__ luma, uint8_t* __restrict__ y, size_t pitch, int W, int H, float mul,
-    float add) {
-  const int Y = blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
+    float add, Fmt<B> f) {
+  using E = typename Sample<B>::type;
+  constexpr int PPL = 16 / B;                  // pixels per lane and store
+  constexpr int LPR = B == 1 ? 64 : kThreads;  // lanes per row
+  const int Y = blockIdx.x * (kThreads / LPR) + threadIdx.x / LPR;
   if (Y >= H) return;
-  const int l = threadIdx.x & 63;
+  const int l = threadIdx.x & (LPR - 1);
   const float* __restrict__ in = luma + (size_t)Y * W;
-  uint8_t* __restrict__ orow = y + (size_t)Y * pitch;
-  auto q = [&](float v) { return quantise(fmaf(v, mul, add)); };
-  const int head = min((int)((16 - ((uintptr_t)orow & 15)) & 15), W);
-  if (l < head) orow[l] = (uint8_t)q(in[l]);
-  const int ng = (W - head) >> 4;
-  for (int g = l; g < ng; g += 64) {
-    const int X = head + 16 * g;
+  uint8_t* __restrict__ obytes = y + (size_t)Y * pitch;
+  E* __restrict__ orow = reinterpret_cast<E*>(obytes);
+  auto q = [&](float v) { return quantise<B>(fmaf(v, mul, add), f); };
+  const int head = min((int)((16 - ((uintptr_t)obytes & 15)) & 15) >> (B - 1), W);
+  if (l < head) orow[l] = (E)q(in[l]);
+  const int ng = (W - head) >> (B == 1 ? 4 : 3);  // groups of PPL pixels
+  for (int g = l; g < ng; g += LPR) {
+    const int X = head + PPL * g;
     uint32_t o[4];
+    if constexpr (B == 1) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const float4u v = *reinterpret_cast<const float4u*>(in + X + 4 * i);
-      o[i] = q(v.x) | q(v.y) << 8 | q(v.z) << 16 | q(v.w) << 24;
+      for (int i = 0; i < 4; i++) {
+        const float4u v = *reinterpret_cast<const float4u*>(in + X + 4 * i);
+        o[i] = q(v.x) | q(v.y) << 8 | q(v.z) << 16 | q(v.w) << 24;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const float4u v = *reinterpret_cast<const float4u*>(in + X + 4 * i);
+        o[2 * i] = q(v.x) | q(v.y) << 16;
+        o[2 * i + 1] = q(v.z) | q(v.w) << 16;
+      }
     }
     *reinterpret_cast<uint4*>(orow + X) = make_uint4(o[0], o[1], o[2], o[3]);
   }
-  const int t = head + 16 * ng + l;  // fewer than 16 pixels are left
-  if (t < W) orow[t] = (uint8_t)q(in[t]);
+  const int t = head + PPL * ng + l;  // fewer than 16 / B pixels are left
+  if (t < W) orow[t] = (E)q(in[t]);
 }
 
-}  // namespace
+Fmt<2> deep_fmt(uint32_t bits, bool msb) {
+  return Fmt<2>{msb ? (int)(16 - bits) : 0, (float)((1u << bits) - 1u)};
+}
 
-int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
-                     uint32_t scale, uint32_t pad, bool full_range, hipStream_t s) {
-  SRCNN_PROFILE("yuv_upscale_luma", s);
-  const float off = full_range ? 0.0f : 16.0f, div = full_range ? 255.0f : 219.0f;
-#define SRCNN_YUV_LUMA(S)                                                                    \
-  {                                                                                          \
-    const uint32_t tx = tiles(w, Tile<S, false>::JX), ty = tiles(h, Tile<S, false>::JY);     \
-    hipLaunchKernelGGL(yuv_upscale_luma_kernel<S>, dim3(tx* ty), dim3(kThreads), 0, s, y,    \
-                       (size_t)pitch_y, plane, (int)w, (int)h, (int)pad, (int)tx, off, div); \
+template <int B>
+int launch_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                uint32_t scale, uint32_t pad, float off, float div, Fmt<B> f, hipStream_t s) {
+#define SRCNN_YUV_LUMA(S)                                                                      \
+  {                                                                                            \
+    const uint32_t tx = tiles(w, Tile<S, false>::JX), ty = tiles(h, Tile<S, false>::JY);       \
+    hipLaunchKernelGGL((yuv_upscale_luma_kernel<S, B>), dim3(tx* ty), dim3(kThreads), 0, s, y, \
+                       (size_t)pitch_y, plane, (int)w, (int)h, (int)pad, (int)tx, off, div, f); \
   }
   switch (scale) {
     case 1: SRCNN_YUV_LUMA(1); break;
@@ -206,46 +299,113 @@ int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t 
   return SRCNN_OK;
 }
 
-int upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
-                      uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
-                      uint32_t oh, uint32_t scale, hipStream_t s) {
-  SRCNN_PROFILE("upscale_planes_u8", s);
-#define SRCNN_YUV_PLANES(S)                                                                    \
-  {                                                                                            \
-    const uint32_t tx = tiles(pw, Tile<S, true>::JX), ty = tiles(ph, Tile<S, true>::JY);       \
-    hipLaunchKernelGGL(upscale_planes_u8_kernel<S>, dim3(tx* ty, 2), dim3(kThreads), 0, s,     \
-                       src0, src1, (size_t)src_pitch, (int)pw, (int)ph, dst0, dst1,            \
-                       (size_t)dst_pitch, (int)ow, (int)oh, (int)tx);                          \
+template <int B, int NCH>
+int launch_planes(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
+                  uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
+                  uint32_t oh, uint32_t scale, Fmt<B> f, hipStream_t s) {
+#define SRCNN_YUV_PLANES(S)                                                                       \
+  {                                                                                               \
+    const uint32_t tx = tiles(pw, Tile<S, true>::JX), ty = tiles(ph, Tile<S, true>::JY);          \
+    hipLaunchKernelGGL((upscale_planes_kernel<S, B, NCH>), dim3(tx* ty, NCH == 1 ? 2 : 1),        \
+                       dim3(kThreads), 0, s, src0, src1, (size_t)src_pitch, (int)pw, (int)ph,     \
+                       dst0, dst1, (size_t)dst_pitch, (int)ow, (int)oh, (int)tx, f);              \
   }
   switch (scale) {
     case 1: SRCNN_YUV_PLANES(1); break;
     case 2: SRCNN_YUV_PLANES(2); break;
     case 3: SRCNN_YUV_PLANES(3); break;
     case 4: SRCNN_YUV_PLANES(4); break;
-    default: return fail(SRCNN_ERR_INVALID, "upscale_planes_u8: scale %u has no kernel", scale);
+    default: return fail(SRCNN_ERR_INVALID, "upscale_planes: scale %u has no kernel", scale);
   }
 #undef SRCNN_YUV_PLANES
   SRCNN_LAUNCH_TRY();
   return SRCNN_OK;
 }
 
+}  // namespace
+
+int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                     uint32_t scale, uint32_t pad, bool full_range, hipStream_t s) {
+  SRCNN_PROFILE("yuv_upscale_luma", s);
+  const float off = full_range ? 0.0f : 16.0f, div = full_range ? 255.0f : 219.0f;
+  return launch_luma<1>(y, pitch_y, plane, w, h, scale, pad, off, div, Fmt<1>{}, s);
+}
+
+int yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                       uint32_t scale, uint32_t pad, uint32_t bits, bool msb, bool full_range,
+                       hipStream_t s) {
+  if (bits == 8) return yuv_upscale_luma(static_cast<const uint8_t*>(y), pitch_y, plane, w, h, scale, pad, full_range, s);
+  SRCNN_PROFILE("yuv_upscale_luma16", s);
+  const float up = (float)(1u << (bits - 8));  // exact
+  const float off = full_range ? 0.0f : 16.0f * up;
+  const float div = full_range ? (float)((1u << bits) - 1u) : 219.0f * up;
+  return launch_luma<2>(static_cast<const uint8_t*>(y), pitch_y, plane, w, h, scale, pad, off, div,
+                        deep_fmt(bits, msb), s);
+}
+
+int upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
+                      uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
+                      uint32_t oh, uint32_t scale, hipStream_t s) {
+  SRCNN_PROFILE("upscale_planes_u8", s);
+  return launch_planes<1, 1>(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
+                             Fmt<1>{}, s);
+}
+
+int upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw, uint32_t ph,
+                   void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
+                   uint32_t scale, uint32_t bits, bool msb, bool semiplanar, hipStream_t s) {
+  const uint8_t *a = static_cast<const uint8_t*>(src0), *b = static_cast<const uint8_t*>(src1);
+  uint8_t *A = static_cast<uint8_t*>(dst0), *Bp = static_cast<uint8_t*>(dst1);
+  if (bits == 8 && !semiplanar)
+    return upscale_planes_u8(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, s);
+  SRCNN_PROFILE("upscale_planes", s);
+  if (bits == 8)
+    return launch_planes<1, 2>(a, nullptr, src_pitch, pw, ph, A, nullptr, dst_pitch, ow, oh, scale,
+                               Fmt<1>{}, s);
+  const Fmt<2> f = deep_fmt(bits, msb);
+  if (semiplanar)
+    return launch_planes<2, 2>(a, nullptr, src_pitch, pw, ph, A, nullptr, dst_pitch, ow, oh, scale,
+                               f, s);
+  return launch_planes<2, 1>(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, f, s);
+}
+
 int yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
                      bool full_range, hipStream_t s) {
   SRCNN_PROFILE("yuv_compose_luma", s);
   const float mul = full_range ? 255.0f : 219.0f, add = full_range ? 0.0f : 16.0f;
-  hipLaunchKernelGGL(yuv_compose_luma_kernel, dim3(tiles(H, kThreads / 64)), dim3(kThreads), 0, s,
-                     luma, y, (size_t)pitch_y, (int)W, (int)H, mul, add);
+  hipLaunchKernelGGL(yuv_compose_luma_kernel<1>, dim3(tiles(H, kThreads / 64)), dim3(kThreads), 0,
+                     s, luma, y, (size_t)pitch_y, (int)W, (int)H, mul, add, Fmt<1>{});
+  SRCNN_LAUNCH_TRY();
+  return SRCNN_OK;
+}
+
+int yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                       uint32_t bits, bool msb, bool full_range, hipStream_t s) {
+  if (bits == 8) return yuv_compose_luma(luma, static_cast<uint8_t*>(y), pitch_y, W, H, full_range, s);
+  SRCNN_PROFILE("yuv_compose_luma16", s);
+  const float up = (float)(1u << (bits - 8));  // exact
+  const float mul = full_range ? (float)((1u << bits) - 1u) : 219.0f * up;
+  const float add = full_range ? 0.0f : 16.0f * up;
+  hipLaunchKernelGGL(yuv_compose_luma_kernel<2>, dim3(H), dim3(kThreads), 0,
+                     s, luma, static_cast<uint8_t*>(y), (size_t)pitch_y, (int)W, (int)H, mul, add,
+                     deep_fmt(bits, msb));
   SRCNN_LAUNCH_TRY();
   return SRCNN_OK;
 }
 
 int preload_yuv() {
-  const void* k[] = {(const void*)yuv_upscale_luma_kernel<1>,  (const void*)yuv_upscale_luma_kernel<2>,
-                     (const void*)yuv_upscale_luma_kernel<3>,  (const void*)yuv_upscale_luma_kernel<4>,
-                     (const void*)upscale_planes_u8_kernel<1>, (const void*)upscale_planes_u8_kernel<2>,
-                     (const void*)upscale_planes_u8_kernel<3>, (const void*)upscale_planes_u8_kernel<4>,
-                     (const void*)yuv_compose_luma_kernel};
-  return resolve_kernels(k, 9);
+#define SRCNN_YUV_SCALES(K, ...) \
+  (const void*)K<1, __VA_ARGS__>, (const void*)K<2, __VA_ARGS__>, (const void*)K<3, __VA_ARGS__>, (const void*)K<4, __VA_ARGS__>
+  const void* k[] = {SRCNN_YUV_SCALES(yuv_upscale_luma_kernel, 1),
+                     SRCNN_YUV_SCALES(yuv_upscale_luma_kernel, 2),
+                     SRCNN_YUV_SCALES(upscale_planes_kernel, 1, 1),
+                     SRCNN_YUV_SCALES(upscale_planes_kernel, 1, 2),
+                     SRCNN_YUV_SCALES(upscale_planes_kernel, 2, 1),
+                     SRCNN_YUV_SCALES(upscale_planes_kernel, 2, 2),
+                     (const void*)yuv_compose_luma_kernel<1>,
+                     (const void*)yuv_compose_luma_kernel<2>};
+#undef SRCNN_YUV_SCALES
+  return resolve_kernels(k, (int)(sizeof(k) / sizeof(k[0])));
 }
 
 }  // namespace srcnn

@@ -286,6 +286,30 @@ void ConfigBasedDataPipeline::super_resolve_yuv(const srcnn_yuv_frame& src, cons
         "upscale_yuv");
 }
 
+void ConfigBasedDataPipeline::super_resolve_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src,
+                                                  const srcnn_yuv_frame& dst, unsigned w, unsigned h, unsigned scale,
+                                                  void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_frame needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  if (stream) {
+    check(srcnn_upscale_frame(&nt, &fmt, &src, &dst, w, h, scale, _context->fptr(_flat_params), ws, ws_bytes, stream),
+          "upscale_frame");
+    return;
+  }
+  if (!_upscale_frame_kernel) {
+    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
+                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
+                             " -D F3=" + std::to_string(nt.f3);
+    _upscale_frame_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame", 0, 0, 0, false, args);
+  }
+  srcnn::Context::Launch l(*_context, *_upscale_frame_kernel);
+  check(srcnn_upscale_frame(&nt, &fmt, &src, &dst, w, h, scale, _context->fptr(_flat_params), ws, ws_bytes,
+                            _context->stream()),
+        "upscale_frame");
+}
+
 bool ConfigBasedDataPipeline::evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& q_net,
                                        QualityReport& q_bicubic) {
   check_initialized(LOAD_KERNEL_LAYERS);

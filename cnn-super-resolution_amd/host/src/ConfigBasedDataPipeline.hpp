@@ -123,6 +123,14 @@ class ConfigBasedDataPipeline : public DataPipeline {
   void super_resolve_yuv(const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst, unsigned w, unsigned h,
                          unsigned cx, unsigned cy, unsigned scale, bool full_range, void* ws, size_t ws_bytes,
                          srcnn_stream_t stream = nullptr);
+  /** super_resolve_yuv for every frame format of DESIGN.md 15 (8 to 16 bits
+   * per sample, planar or semi-planar chroma; `fmt` also holds the subsampling
+   * and the range): one srcnn_upscale_frame call, enqueued, counted and timed
+   * in the same way, as kernel 'srcnn_upscale_frame'; the workspace is
+   * super_resolve_yuv_workspace_bytes. */
+  void super_resolve_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst,
+                           unsigned w, unsigned h, unsigned scale, void* ws, size_t ws_bytes,
+                           srcnn_stream_t stream = nullptr);
   /** 0 if the net, the size or the scale is invalid (srcnn_last_error says why) */
   size_t super_resolve_yuv_workspace_bytes(unsigned w, unsigned h, unsigned scale);
   /** Training pairs of one full-size image, cut on the device: one
@@ -237,6 +245,7 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
   Kernel* _upscale_yuv_kernel = nullptr;
+  Kernel* _upscale_frame_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
   Kernel* _planes_kernel = nullptr;
 

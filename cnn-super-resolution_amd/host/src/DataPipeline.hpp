@@ -93,6 +93,27 @@ class DataPipeline {
   Event yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y, bool full_range,
                          Event* ev = nullptr);
 
+  /** Extension, samples of 8 to 16 bits and semi-planar chroma:
+   * yuv_upscale_luma for a Y plane of `bits` bits per sample, one byte at 8
+   * bits, else a 16-bit word with the value in its low (msb false) or high
+   * bits; pitch_y in bytes (srcnn_yuv_upscale_luma16). */
+  Event yuv_upscale_luma16(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& gpu_buf_luma_padded,
+                           size_t scale, size_t total_padding, unsigned bits, bool msb, bool full_range,
+                           Event* ev = nullptr);
+
+  /** Extension: a frame's chroma of pw x ph bicubic x `scale`, rounded and
+   * clamped to `bits` bits, the top-left ow x oh: two planes into dst0 and
+   * dst1, or, semiplanar, src0's (U, V) pairs into dst0 with src1 and dst1
+   * nullptr; pitches in bytes (srcnn_upscale_planes). */
+  Event upscale_planes(MemoryHandle src0, MemoryHandle src1, size_t src_pitch, size_t pw, size_t ph,
+                       MemoryHandle dst0, MemoryHandle dst1, size_t dst_pitch, size_t ow, size_t oh, size_t scale,
+                       unsigned bits, bool msb, bool semiplanar, Event* ev = nullptr);
+
+  /** Extension: the net's luma (w x h floats) back into a Y plane of `bits`
+   * bits per sample (srcnn_yuv_compose_luma16). */
+  Event yuv_compose_luma16(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y, unsigned bits,
+                           bool msb, bool full_range, Event* ev = nullptr);
+
   /** Extension, the inverse of the upscale: `img` antialiased-bicubic
    * downscaled by `scale` (1..4) on the device into `out`, RGBA of
    * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
@@ -194,6 +215,9 @@ class DataPipeline {
   Kernel* _yuv_upscale_luma_kernel = nullptr;
   Kernel* _upscale_planes_u8_kernel = nullptr;
   Kernel* _yuv_compose_luma_kernel = nullptr;
+  Kernel* _yuv_upscale_luma16_kernel = nullptr;
+  Kernel* _upscale_planes_kernel = nullptr;
+  Kernel* _yuv_compose_luma16_kernel = nullptr;
   Kernel* _downscale_kernel = nullptr;
   Kernel* _gather_tiles_kernel = nullptr;
   Kernel* _gather_batch_kernel = nullptr;

@@ -36,23 +36,36 @@ uint64_t parse_dim(const std::string& v, char tag) {
   return n;
 }
 
+/** The depth of "420p10", "422p12", ...: the subsampling, then 'p', then one of
+ * 9, 10, 12, 14 and 16; 0 for anything else. */
+uint32_t deep_bits(const std::string& v) {
+  if (v.size() < 5 || v.size() > 6 || v[3] != 'p') return 0;
+  const std::string n = v.substr(4);
+  for (const char* ok : {"9", "10", "12", "14", "16"})
+    if (n == ok) return uint32_t(std::stoi(n));
+  return 0;
+}
+
 void set_chroma(Header& hd, const std::string& v) {
-  if (v == "420jpeg" || v == "420mpeg2" || v == "420paldv" || v == "420") {
+  const std::string sub = v.substr(0, 3);
+  const uint32_t deep = deep_bits(v);
+  if (v == "420jpeg" || v == "420mpeg2" || v == "420paldv" || v == "420" || (deep && sub == "420")) {
     hd.cx = 2;
     hd.cy = 2;
-  } else if (v == "422") {
+  } else if (v == "422" || (deep && sub == "422")) {
     hd.cx = 2;
     hd.cy = 1;
-  } else if (v == "444") {
+  } else if (v == "444" || (deep && sub == "444")) {
     hd.cx = 1;
     hd.cy = 1;
   } else if (v == "mono") {
     throw IOException("unsupported Y4M chroma 'Cmono': no chroma planes");
   } else if (v.find('p') != std::string::npos && v.find("pal") == std::string::npos) {
-    throw IOException("unsupported Y4M chroma 'C" + v + "': more than 8 bits per sample");
+    throw IOException("unsupported Y4M chroma 'C" + v + "': the depths above 8 bits are p9, p10, p12, p14 and p16");
   } else {
     throw IOException("unsupported Y4M chroma 'C" + v + "'");
   }
+  hd.bits = deep ? deep : 8;
   hd.chroma = v;
   hd.has_chroma = true;
 }

@@ -1,11 +1,13 @@
-// YUV4MPEG2 (Y4M) streams for `cnn upscale`: planar Y'CbCr video, 8 bits per
-// sample, one text header line and one "FRAME" line in front of every frame's
-// Y, U and V planes.
+// YUV4MPEG2 (Y4M) streams for `cnn upscale`: planar Y'CbCr video, one text
+// header line and one "FRAME" line in front of every frame's Y, U and V
+// planes.  A sample is one byte, or, in the formats with 9 to 16 bits, a
+// little-endian 16-bit word with the value in its low bits.
 //
 // Read: header tokens W, H, F, I, A, C and X...; chroma C420jpeg, C420mpeg2,
-// C420paldv, C420 (4:2:0), C422 and C444, C420jpeg when there is no C token;
-// progressive only (Ip or I?); interlaced streams, Cmono and every format with
-// more than 8 bits are rejected with a message.  The luma range comes from an
+// C420paldv, C420 (4:2:0), C422 and C444 at 8 bits, C420pN, C422pN and C444pN
+// with N = 9, 10, 12, 14 or 16 above, C420jpeg when there is no C token;
+// progressive only (Ip or I?); interlaced streams, Cmono and every other
+// format are rejected with a message.  The luma range comes from an
 // XCOLORRANGE=FULL|LIMITED token and is limited without one.  FRAME lines may
 // carry parameters, which are skipped.
 // The reader takes untrusted input: a header or FRAME line is at most 4096
@@ -29,6 +31,7 @@ constexpr size_t kMaxLine = 4096;  // header and FRAME lines, the newline includ
 struct Header {
   uint32_t w = 0, h = 0;
   uint32_t cx = 2, cy = 2;         // chroma subsampling: 2x2, 2x1 or 1x1
+  uint32_t bits = 8;               // per sample: 8, or 9..16 in two bytes
   std::string chroma = "420jpeg";  // the C token's value
   bool has_chroma = false;         // the input had a C token
   std::string rate, interlace, aspect;  // the F, I and A tokens' values ("" = absent)
@@ -37,8 +40,9 @@ struct Header {
 
   uint32_t cw() const { return (w + cx - 1) / cx; }
   uint32_t ch() const { return (h + cy - 1) / cy; }
-  size_t luma_bytes() const { return size_t(w) * h; }
-  size_t chroma_bytes() const { return size_t(cw()) * ch(); }  // one plane
+  size_t sample_bytes() const { return bits > 8 ? 2 : 1; }
+  size_t luma_bytes() const { return size_t(w) * h * sample_bytes(); }
+  size_t chroma_bytes() const { return size_t(cw()) * ch() * sample_bytes(); }  // one plane
   size_t frame_bytes() const { return luma_bytes() + 2 * chroma_bytes(); }
   /** the header of the stream `scale` times as large */
   Header scaled(unsigned scale) const;

@@ -1,6 +1,7 @@
 // y4m_tool -- test driver of the Y4M reader and writer (no device needed):
 //   y4m_tool IN OUT          read the YUV4MPEG2 stream IN and write it as OUT
-// Prints "<w> <h> <cx> <cy> <full|limited> <frames>".  Exit status 1 and the
+// Prints "<w> <h> <cx> <cy> <full|limited> <frames>", and the bits per sample
+// as a seventh field where they exceed 8.  Exit status 1 and the
 // IOException message on unsupported / corrupt input; the frames in front of a
 // truncated one are written.
 #include <fstream>
@@ -34,7 +35,9 @@ int main(int argc, char** argv) {
       rc = 1;
     }
     std::cout << hd.w << " " << hd.h << " " << hd.cx << " " << hd.cy << " " << (hd.full_range ? "full" : "limited")
-              << " " << frames << std::endl;
+              << " " << frames;
+    if (hd.bits > 8) std::cout << " " << hd.bits;
+    std::cout << std::endl;
     return rc;
   } catch (const std::exception& e) {
     std::cout << "[ERROR] " << e.what() << std::endl;

@@ -16,12 +16,13 @@
 //           net and the composition all run on the device (srcnn_upscale), and
 //           every output pixel passes through the net.  --scale 1 is the
 //           "same size, no border frame" mode for inputs that are already scaled.
-//           If IN starts with the YUV4MPEG2 magic it is a Y4M video (8-bit
-//           4:2:0, 4:2:2 or 4:4:4, progressive) and is streamed: every frame
-//           is upscaled by S on the device as planar Y'CbCr -- luma through
-//           the net, chroma plain bicubic (srcnn_upscale_yuv) -- and OUT is a
-//           Y4M of S times the size with the same F, I, A, C and XCOLORRANGE
-//           tokens.  Two frame slots, each with its own stream, pinned host
+//           If IN starts with the YUV4MPEG2 magic it is a Y4M video (8-bit,
+//           or 9 to 16 bits as C420p10 and its kin; 4:2:0, 4:2:2 or 4:4:4,
+//           progressive) and is streamed: every frame is upscaled by S on the
+//           device as planar Y'CbCr -- luma through the net, chroma plain
+//           bicubic (srcnn_upscale_yuv; srcnn_upscale_frame above 8 bits) --
+//           and OUT is a Y4M of S times the size and the same depth with the
+//           same F, I, A, C and XCOLORRANGE tokens.  Two frame slots, each with its own stream, pinned host
 //           buffers, device frames and workspace: while one slot computes, the
 //           next frame is read into the other; a slot is drained and its frame
 //           written before it is reused, so frames leave in order (--slots 1:
@@ -151,7 +152,8 @@ void usage() {
          "  upscale               upscale mode: IN is a low-resolution image, OUT the image\n"
          "                        of --scale times the size (bicubic + net on the device;\n"
          "                        no un-enhanced border frame)\n"
-         "                        A Y4M video (YUV4MPEG2; 8-bit 4:2:0, 4:2:2 or 4:4:4) is\n"
+         "                        A Y4M video (YUV4MPEG2; 4:2:0, 4:2:2 or 4:4:4 at 8 bits,\n"
+         "                        or at 9 to 16 as C420p10 and its kin) is\n"
          "                        streamed frame by frame: luma through the net, chroma\n"
          "                        bicubic, OUT a Y4M of --scale times the size\n"
          "  downscale             downscale mode: IN is a full-size image, OUT the image of\n"
@@ -411,7 +413,8 @@ struct FrameSlot {
   }
   static srcnn_yuv_frame planes(void* base, const srcnn::y4m::Header& hd) {
     uint8_t* b = static_cast<uint8_t*>(base);
-    return srcnn_yuv_frame{b, b + hd.luma_bytes(), b + hd.luma_bytes() + hd.chroma_bytes(), hd.w, hd.cw()};
+    const uint32_t B = uint32_t(hd.sample_bytes());  // pitches are bytes
+    return srcnn_yuv_frame{b, b + hd.luma_bytes(), b + hd.luma_bytes() + hd.chroma_bytes(), hd.w * B, hd.cw() * B};
   }
   void init(const srcnn::y4m::Header& in, const srcnn::y4m::Header& out, size_t ws_bytes, bool own_stream) {
     if (own_stream) srcnn::check(srcnn_stream_create(&stream), "stream_create");
@@ -425,8 +428,9 @@ struct FrameSlot {
   }
 };
 
-/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_yuv.  Any
- * failed call throws, which ends the run before another frame is started. */
+/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_yuv, or,
+ * with more than 8 bits per sample, through srcnn_upscale_frame.  Any failed
+ * call throws, which ends the run before another frame is started. */
 int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   namespace y4m = srcnn::y4m;
   y4m::Header hd = y4m::read_header(in);
@@ -435,6 +439,8 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
     hd.has_range = true;
   }
   const y4m::Header ohd = hd.scaled(a.scale);
+  // a deep stream holds its values in the low bits of two-byte words, in planes
+  const srcnn_yuv_format fmt{hd.bits, 0, SRCNN_YUV_PLANAR, hd.cx, hd.cy, hd.full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED};
   std::cout << "Y4M video: " << hd.w << "x" << hd.h << " C" << hd.chroma << ", "
             << (hd.full_range ? "full" : "limited") << " range -> " << ohd.w << "x" << ohd.h << std::endl;
   const size_t ws_bytes = p.super_resolve_yuv_workspace_bytes(hd.w, hd.h, a.scale);
@@ -474,8 +480,11 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
       break;
     }
     srcnn::check(srcnn_memcpy_h2d(s.dev_in, s.host_in, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
-    p.super_resolve_yuv(s.src, s.dst, hd.w, hd.h, hd.cx, hd.cy, a.scale, hd.full_range, s.ws, ws_bytes,
-                        own_streams ? s.stream : nullptr);
+    if (hd.bits > 8)
+      p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
+    else
+      p.super_resolve_yuv(s.src, s.dst, hd.w, hd.h, hd.cx, hd.cy, a.scale, hd.full_range, s.ws, ws_bytes,
+                          own_streams ? s.stream : nullptr);
     s.busy = true;
   }
   for (unsigned i = 0; i < a.slots; ++i) drain(slots[(k + i) % a.slots]);  // the oldest first

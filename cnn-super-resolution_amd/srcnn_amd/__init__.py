@@ -52,6 +52,20 @@ class YuvFrame(ctypes.Structure):
 
 _FP = ctypes.POINTER(YuvFrame)
 
+
+class YuvFormat(ctypes.Structure):
+    """srcnn_yuv_format: bits per sample (8..16), msb (1: the value sits in the
+    high bits of its 16-bit word, P010 style), layout (YUV_PLANAR or
+    YUV_SEMIPLANAR), the chroma subsampling cx x cy and the range."""
+    _fields_ = [("bits", _U), ("msb", _U), ("layout", _U), ("cx", _U), ("cy", _U), ("range", ctypes.c_int32)]
+
+    def __repr__(self):
+        return "YuvFormat(bits=%d, msb=%d, layout=%d, cx=%d, cy=%d, range=%d)" % (
+            self.bits, self.msb, self.layout, self.cx, self.cy, self.range)
+
+
+_MP = ctypes.POINTER(YuvFormat)
+
 # name -> (restype, argtypes); int restype = status code checked by _call
 SIGNATURES = {
     "srcnn_abi_version": (_I, []),
@@ -98,6 +112,9 @@ SIGNATURES = {
     "srcnn_yuv_upscale_luma": (_I, [_P, _U, _P, _U, _U, _U, _U, _I, _P]),
     "srcnn_upscale_planes_u8": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _P]),
     "srcnn_yuv_compose_luma": (_I, [_P, _P, _U, _U, _U, _I, _P]),
+    "srcnn_yuv_upscale_luma16": (_I, [_P, _U, _P, _U, _U, _U, _U, _U, _U, _I, _P]),
+    "srcnn_yuv_compose_luma16": (_I, [_P, _P, _U, _U, _U, _U, _U, _I, _P]),
+    "srcnn_upscale_planes": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _U, _U, _U, _P]),
     "srcnn_downscale_rgba": (_I, [_P, _P, _U, _U, _U, _P]),
     "srcnn_gather_tiles": (_I, [_P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _I, _P, _P, _P]),
     "srcnn_gather_batch": (_I, [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P]),
@@ -110,6 +127,7 @@ SIGNATURES = {
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_upscale_yuv_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale_yuv": (_I, [_NP, _FP, _FP, _U, _U, _U, _U, _U, _I, _P, _P, _S, _P]),
+    "srcnn_upscale_frame": (_I, [_NP, _MP, _FP, _FP, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_evaluate_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_evaluate": (_I, [_NP, _P, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
@@ -167,6 +185,8 @@ COMM_ID_BYTES = 128
 PIX_LUMA_F32, PIX_RGB8, PIX_RGBA8 = 1, 3, 4
 # range of a Y'CbCr frame's luma (SRCNN_YUV_*)
 YUV_LIMITED, YUV_FULL = 0, 1
+# chroma layout of a frame (SRCNN_YUV_*): two planes, or one plane of (U, V) pairs
+YUV_PLANAR, YUV_SEMIPLANAR = 0, 1
 
 
 def _call(name, *args):
@@ -383,6 +403,28 @@ def yuv_compose_luma(luma, y, pitch_y, W, H, yuv_range, s=None):
     _call("srcnn_yuv_compose_luma", ptr(luma), ptr(y), pitch_y, W, H, yuv_range, s)
 
 
+def yuv_upscale_luma16(y, pitch_y, luma_padded, w, h, scale, pad, bits, msb, yuv_range, s=None):
+    """yuv_upscale_luma for samples of `bits` (8..16) bits: one byte at 8 bits,
+    else a 16-bit word with the value in its low (msb 0) or high (msb 1) bits;
+    pitch_y in bytes (srcnn_yuv_upscale_luma16)."""
+    _call("srcnn_yuv_upscale_luma16", ptr(y), pitch_y, ptr(luma_padded), w, h, scale, pad, bits, msb, yuv_range, s)
+
+
+def yuv_compose_luma16(luma, y, pitch_y, W, H, bits, msb, yuv_range, s=None):
+    """luma [H][W] f32 -> Y [H][W] samples of `bits` bits, rows pitch_y bytes
+    apart (srcnn_yuv_compose_luma16)."""
+    _call("srcnn_yuv_compose_luma16", ptr(luma), ptr(y), pitch_y, W, H, bits, msb, yuv_range, s)
+
+
+def upscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale, bits, msb, layout, s=None):
+    """A frame's chroma [ph][pw] -> the top-left ow x oh of its bicubic x scale,
+    rounded and clamped to `bits` bits: YUV_PLANAR: two planes in, two out;
+    YUV_SEMIPLANAR: src0 / dst0 hold (U, V) pairs, src1 and dst1 are None;
+    pitches in bytes (srcnn_upscale_planes)."""
+    _call("srcnn_upscale_planes", ptr(src0), ptr(src1), src_pitch, pw, ph, ptr(dst0), ptr(dst1), dst_pitch, ow, oh,
+          scale, bits, msb, layout, s)
+
+
 def downscale_rgba(rgba, small, W, H, scale, s=None):
     """rgba [H][W][4] u8 -> antialiased bicubic / scale, small
     [H//scale][W//scale][4] u8, alpha 255 (srcnn_downscale_rgba)."""
@@ -586,6 +628,19 @@ def upscale_yuv(net, src, dst, w, h, cx, cy, scale, yuv_range, params, ws, ws_by
     yuv_compose_luma, and upscale_planes_u8 for the chroma."""
     _call("srcnn_upscale_yuv", ctypes.byref(net), ctypes.byref(src), ctypes.byref(dst), w, h, cx, cy,
           scale, yuv_range, ptr(params), ptr(ws), ws_bytes, s)
+
+
+def yuv_format(bits=8, msb=0, layout=YUV_PLANAR, cx=2, cy=2, yuv_range=YUV_LIMITED):
+    """A YuvFormat; the defaults are 8-bit planar 4:2:0 at limited range."""
+    return YuvFormat(bits, msb, layout, cx, cy, yuv_range)
+
+
+def upscale_frame(net, fmt, src, dst, w, h, scale, params, ws, ws_bytes, s=None):
+    """upscale_yuv for every YuvFormat: 8 to 16 bits per sample, planar or
+    semi-planar (NV12, P010: the frames' u holds the (U, V) pairs, v is None);
+    the workspace is upscale_yuv_workspace_bytes (srcnn_upscale_frame)."""
+    _call("srcnn_upscale_frame", ctypes.byref(net), ctypes.byref(fmt) if fmt is not None else None,
+          ctypes.byref(src), ctypes.byref(dst), w, h, scale, ptr(params), ptr(ws), ws_bytes, s)
 
 
 def evaluate_workspace_bytes(net, W, H, scale):

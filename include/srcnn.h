@@ -245,6 +245,50 @@ SRCNN_API int srcnn_upscale_planes_u8(const uint8_t* src0, const uint8_t* src1,
 SRCNN_API int srcnn_yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W,
                                      uint32_t H, int range, srcnn_stream_t stream);
 
+/* The same three for samples of 8 to 16 bits and for semi-planar chroma (NV12,
+ * P010 / P012 / P016): DESIGN.md 15 is the spec.  At bits = 8 a sample is one
+ * byte; above, it is a 16-bit little-endian word x that holds the value
+ *   msb = 0   Y = x                  (Y4M's p10 family; nothing is masked)
+ *   msb = 1   Y = x >> (16 - bits)   (P010 family); msb = 1 at 8 bits is invalid
+ * A written sample is q = clamp(rint(.), 0, 2^bits - 1), stored as q or as
+ * q << (16 - bits) with the low bits zero.  With k = 2^(bits-8):
+ *   SRCNN_YUV_FULL     v = Y / (2^bits - 1)       Y = rint(v * (2^bits - 1))
+ *   SRCNN_YUV_LIMITED  v = (Y - 16 k) / (219 k)   Y = rint(v * 219 k + 16 k)
+ * in fp32; at bits = 8 these are the formulas above, and the three calls give
+ * the results of the 8-bit calls byte for byte.  Chroma values are resampled as
+ * they are and clamped to [0, 2^bits - 1] after rounding to nearest.
+ *
+ * Pitches are in bytes and at least the row's bytes: with B bytes per sample
+ * w*B for luma, pw*B for a planar chroma plane, 2*pw*B for a semi-planar one.
+ * For two-byte samples every plane address and every pitch must be even.  The
+ * bytes between a row's end and the next row are never read and never written.
+ *
+ * srcnn_upscale_planes: layout SRCNN_YUV_PLANAR: src0, src1 [ph][pw] -> dst0,
+ * dst1 [oh][ow] as srcnn_upscale_planes_u8 does.  SRCNN_YUV_SEMIPLANAR: src0
+ * [ph][pw][2] holds (U, V) pairs -> dst0 [oh][ow][2]; src1 and dst1 must be
+ * NULL; pw, ow and the crop rule count pairs; every sample equals that of the
+ * planar call on the two de-interleaved planes.  With s = 1 the output is the
+ * source for every sample within [0, 2^bits - 1].
+ *
+ * SRCNN_ERR_INVALID: what the 8-bit calls reject, plus bits outside 8..16, msb
+ * not 0 or 1 or 1 at 8 bits, an unknown layout, an odd address or pitch for
+ * two-byte samples, a plane pointer that the layout does not have (or lacks
+ * one it has), or more than 2^31-1 samples in a plane (a semi-planar chroma
+ * plane counts 2*pw*ph). */
+enum { SRCNN_YUV_PLANAR = 0, SRCNN_YUV_SEMIPLANAR = 1 };
+SRCNN_API int srcnn_yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* luma_padded,
+                                       uint32_t w, uint32_t h, uint32_t scale, uint32_t pad,
+                                       uint32_t bits, uint32_t msb, int range,
+                                       srcnn_stream_t stream);
+SRCNN_API int srcnn_yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W,
+                                       uint32_t H, uint32_t bits, uint32_t msb, int range,
+                                       srcnn_stream_t stream);
+SRCNN_API int srcnn_upscale_planes(const void* src0, const void* src1, uint32_t src_pitch,
+                                   uint32_t pw, uint32_t ph, void* dst0, void* dst1,
+                                   uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t scale,
+                                   uint32_t bits, uint32_t msb, uint32_t layout,
+                                   srcnn_stream_t stream);
+
 /* Training pairs from a full-size image, on the device (an MI355X extension;
  * the reference's pairs are made on the host, one file per sample).  The
  * training-side mirror of the upscaling front end: DESIGN.md 11.1 is the spec.
@@ -535,6 +579,32 @@ SRCNN_API int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src
                                 const srcnn_yuv_frame* dst, uint32_t w, uint32_t h, uint32_t cx,
                                 uint32_t cy, uint32_t scale, int range, const float* params,
                                 void* ws, size_t ws_bytes, srcnn_stream_t stream);
+
+/* srcnn_upscale_yuv for every frame format of DESIGN.md 15: fmt names the
+ * sample format (bits, msb), the chroma layout, the subsampling (cx, cy) and
+ * the range; source and output frame have the same format.  src and dst are
+ * srcnn_yuv_frame: their uint8_t* members are byte addresses whatever the
+ * sample size, their pitches are bytes; with SRCNN_YUV_SEMIPLANAR u holds the
+ * (U, V) pairs and v must be NULL, in src and in dst.  The call is
+ *   srcnn_yuv_upscale_luma16(src->y, pad = f1+f2+f3-3) -> plane
+ *   srcnn_sub_mean, srcnn_forward as in srcnn_upscale_yuv
+ *   srcnn_yuv_compose_luma16(out -> dst->y)
+ *   srcnn_upscale_planes(src->u, src->v -> dst->u, dst->v)
+ * and byte-identical to those calls; with {8, 0, SRCNN_YUV_PLANAR, cx, cy,
+ * range} it is srcnn_upscale_yuv byte for byte.  Stream-ordered, no
+ * allocation; the workspace is srcnn_upscale_yuv_workspace_bytes(net, w, h,
+ * scale) under the same memory contract; of dst it writes the samples of each
+ * row and nothing between the rows.  Errors as the op-level calls and as
+ * srcnn_upscale_yuv, before any launch, plus SRCNN_ERR_INVALID for a null
+ * fmt. */
+typedef struct srcnn_yuv_format {
+  uint32_t bits, msb, layout, cx, cy;
+  int32_t range;
+} srcnn_yuv_format;
+SRCNN_API int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                                  const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst,
+                                  uint32_t w, uint32_t h, uint32_t scale, const float* params,
+                                  void* ws, size_t ws_bytes, srcnn_stream_t stream);
 
 /* "How many dB over bicubic?" in one call: the full-size ground truth rgba
  * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at
