@@ -24,6 +24,14 @@
 //                  4m + 2 + h, each 4 consecutive X values under any tap --
 //                  one ds_read2_b32 per run and part from part-interleaved
 //                  pair images (row runs: R; column runs: T, column-major)
+//                  kD3: in two fp16 parts per operand instead (split.hpp),
+//                  three v_mfma_f32_32x32x16_f16 per k-step where the bf16
+//                  form takes six: delta1 2^e1 and X 2^ex with per-sample
+//                  exponents from bounds (max |delta3| times the two weight
+//                  norms; max |X|), the accumulators 2^EW x the sum (the bias
+//                  column 2^EB x), unscaled in the block reduction.  The X
+//                  images keep their layout and use dwords 0 and 1 of a
+//                  position's three
 //   gB2[n] += sum_p delta2[p][n]                     VALU over delta2^T (kTr:
 //                  per lane over the rows, crossed over lanes in the epilogue)
 // Each wave accumulates over its chunks; at the end the four waves' sums are
@@ -35,6 +43,17 @@
 constexpr int kD6W2 = 2 * 2 * 3 * 512;  // delta1's W2 image, bf16: [t][k][part][lane][8]
 constexpr int kD6W3 = 2 * 3 * 512;      // delta2's W3 image (kD3), bf16: [s][part][lane][8]
 constexpr int kD6Sc = 32 * 36;           // per-wave delta2 transpose scratch (floats)
+
+// kD3: the waves' per-sample maxima in the constant region (dword offsets)
+constexpr int kD6Mxx = 12, kD6Mx3 = 25;
+// kD3: gW1's accumulators hold 2^EW x the sum (the bias column 2^EB x); a
+// sample whose own exponent lies within this window of EW takes its X scale
+// from EW, one outside it moves EW (the accumulators are multiplied by the
+// exact power of two) to kD6ExMid below its own
+constexpr int kD6ExWin = 6, kD6ExMid = 3;
+// no sample's scale lies more than 2^kD6Grow above the largest sample's seen
+// (the accumulators cannot overflow: 2^30 per product, < 2^20 slots per wave)
+constexpr int kD6Grow = 70;
 
 // layer-3 geometry for the kD3 form (delta2 formed here from delta3)
 struct D3Geom {
@@ -233,7 +252,13 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   for (int i = threadIdx.x; i < (2 * L.xbuf + 3) / 4; i += 256) reinterpret_cast<uint4*>(xbuf)[i] = uint4{0u, 0u, 0u, 0u};
   // gW1's third tap tile past tap 80: the ones column (gB1) and zero columns
   // read these constant pair images instead of X (dwords q and q + 6 of part q)
-  if (threadIdx.x < 32) u32[L.cst / 4 + threadIdx.x] = threadIdx.x == 0 || threadIdx.x == 6 ? 0x3F803F80u : 0u;
+  // kD3 (gW1 in two fp16 parts, below): two ones images, at dwords 0 and 3
+  // (sample parity; dwords q, q + 6 of part q < 2), whose constant 2^k each
+  // sample writes at its top; the zero image from dword 16; dwords 12-15 and
+  // 25-28 hold the waves' maxima of |X| and |delta3| (kD6Mxx, kD6Mx3: written
+  // before this store may land, so it leaves them out)
+  if (threadIdx.x < 32 && (!kD3 || threadIdx.x < kD6Mxx || (threadIdx.x >= 16 && threadIdx.x < kD6Mx3)))
+    u32[L.cst / 4 + threadIdx.x] = !kD3 && (threadIdx.x == 0 || threadIdx.x == 6) ? 0x3F803F80u : 0u;
   {
     // delta1's B operand W2^T: tile t, k-step k, lane (c, h), element j <->
     // W2[32 t + c][n] with n = 16 k + 8 h + j (delta2 rows as loaded), or for
@@ -260,7 +285,7 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
 
   uint32_t* const d3u = u32 + L.d3img / 4;  // kD3: the three delta3 buffers
   const int nout3 = dg.w3 * dg.h3;
-  float d3n[2];  // kD3: this thread's delta3 values of a later sample
+  float d3n[2] = {0.0f, 0.0f};  // kD3: this thread's delta3 values of a later sample
   auto d3load = [&](int smp) {
 #pragma unroll
     for (int k = 0; k < 2; k++) {
@@ -288,7 +313,40 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       }
     }
   };
+  // kD3: gW1 / gB1 in two fp16 parts per operand (split.hpp: three MFMAs per
+  // k-step where the bf16 form takes six).  Each sample's delta1 is scaled by
+  // 2^e1 from the bound |delta1| <= max |delta3| . max_n sum_tap |W3[tap][n]| .
+  // max_c sum_n |W2[c][n]| and its X by 2^ex from max |X|; both maxima are
+  // block maxima through the constant region (one more barrier per sample).
+  float* const mxx = smem + L.cst / 4 + kD6Mxx;
+  float* const mx3 = smem + L.cst / 4 + kD6Mx3;
+  auto wave_max = [&](float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+  };
+  auto put_max = [&](float* slot, float v) {
+    v = wave_max(v);
+    if (lane == 0) slot[wave] = v;
+  };
+  // (the same four values in the same order on every thread; scalar)
+  auto take_max_reg = [&](float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+  };
+  auto take_max = [&](const float* slot) {
+    const float v = fmaxf(fmaxf(slot[0], slot[1]), fmaxf(slot[2], slot[3]));
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+  };
+  float m3cur = 0.0f, wnorm = 0.0f;  // max |delta3| of the current sample; the two norms' product
+  int EW = 0, EB = 0, EWmin = 1 << 20, EBmin = 1 << 20;
   if constexpr (kD3) {
+    {
+      // (every wave forms both norms itself: lane = W2's channel, lane & 31 = W3's)
+      float n2 = 0.0f, n3 = 0.0f;
+      for (int n = 0; n < N2; n++) n2 += fabsf(W2[lane * N2 + n]);
+      for (int t = 0; t < dg.f3 * dg.f3; t++) n3 += fabsf(W3[t * N2 + li]);
+      wnorm = take_max_reg(wave_max(n2)) * take_max_reg(wave_max(n3));
+    }
     // delta2's A operand W3^T: k-step s, part q, lane (n, h), element j <->
     // W3[tap of pair slot 8 s + 4 h + (j >> 1), element j & 1][n], zero on
     // the unused elements (d3taps.hpp)
@@ -328,7 +386,9 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     for (int i = threadIdx.x; i < (3 * L.d3buf + 3) / 4; i += 256)  // borders stay zero
       reinterpret_cast<uint4*>(d3u)[i] = uint4{0u, 0u, 0u, 0u};
     if ((int)blockIdx.x < g.batch) d3load(blockIdx.x);
+    put_max(mx3, fmaxf(fabsf(d3n[0]), fabsf(d3n[1])));
     __syncthreads();  // zeroed before the first build
+    m3cur = take_max(mx3);
     d3build(0);       // sample 0 (buffer j % 3 holds sample j)
     if ((int)blockIdx.x + (int)gridDim.x < g.batch) d3load(blockIdx.x + gridDim.x);
   }
@@ -608,8 +668,115 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   for (int it = 0; (int)blockIdx.x + it * (int)gridDim.x < g.batch; it++) {
     const int smp = blockIdx.x + it * gridDim.x;
     uint32_t* const xi = xbuf + (it & 1) * L.xbuf;
+    // ---- kD3: this sample's scales (the same scalars on every thread) ----
+    float s1 = 1.0f, sX = 1.0f;  // 2^e1 for delta1, 2^ex for X
+    float m3next = 0.0f;
+    if constexpr (kD3) {
+      float xm = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kL12Regs; k++) xm = fmaxf(xm, fabsf(xr[k]));
+      // (the two reductions step by step together: one after the other they
+      // were twelve dependent LDS round trips at every sample's top)
+      float dm = fmaxf(fabsf(d3n[0]), fabsf(d3n[1]));  // sample it + 1's, if there is one
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float tx = __shfl_xor(xm, o, 64), td = __shfl_xor(dm, o, 64);
+        xm = fmaxf(xm, tx);
+        dm = fmaxf(dm, td);
+      }
+      if (lane == 0) {
+        mxx[wave] = xm;
+        mx3[wave] = dm;
+      }
+      // sample it + 1's delta3 image into buffer (it + 1) % 3, last read for
+      // sample it - 2 (every wave is past that sample: the barrier at the top
+      // of sample it - 1); read from the first delta2 of sample it + 1 on,
+      // after the second barrier below.  (Ahead of the first: it does not wait
+      // for the scales)
+      if (smp + (int)gridDim.x < g.batch) d3build((it + 1) - 3 * ((it + 1) / 3));
+      __syncthreads();  // (the slots are written again after the barrier below, read before it)
+      const float xmax = take_max(mxx);
+      m3next = take_max(mx3);
+      const float bound = m3cur * wnorm;
+      // (exn >= -123: 2^(exn - kD6ExMid) stays a normal fp32)
+      int e1 = mfma::scale_exp_h(bound), exn = mfma::scale_exp_h(xmax), ex = 0, kb = 0, dW = 0, dB = 0;
+      if (exn < mfma::kScaleMin + kD6ExMid) exn = mfma::kScaleMin + kD6ExMid;
+      if (bound > 0.0f) {
+        // a sample far below the largest seen takes a smaller scale
+        int exc = e1 + exn - kD6ExMid - (EWmin + kD6Grow);
+        if (exc < e1 - (EBmin + kD6Grow)) exc = e1 - (EBmin + kD6Grow);
+        if (exc > 0) e1 = e1 - exc < mfma::kScaleMin ? mfma::kScaleMin : e1 - exc;
+        // the bias column's constant 2^kb (a normal fp16) takes up EB - e1, or EB moves
+        kb = EB - e1;
+        if (kb < -14 || kb > 15) {
+          dB = e1 - EB;
+          EB = e1;
+          kb = 0;
+        }
+        if (xmax > 0.0f) {
+          ex = EW - e1;
+          if (ex > exn || ex < exn - kD6ExWin) {
+            ex = exn - kD6ExMid;
+            dW = e1 + ex - EW;
+            EW = e1 + ex;
+          }
+        }
+        if (EW < EWmin) EWmin = EW;
+        if (EB < EBmin) EBmin = EB;
+      } else {
+        e1 = 0;  // delta1 = 0 throughout: any finite scales do
+        ex = xmax > 0.0f ? exn - kD6ExMid : 0;
+      }
+      s1 = mfma::pow2_h(e1);
+      sX = mfma::pow2_h(ex);
+      if (threadIdx.x == 0) {
+        const uint32_t c = (uint32_t)(kb + 15) << 10;  // 2^kb as fp16
+        u32[L.cst / 4 + 3 * (it & 1)] = u32[L.cst / 4 + 3 * (it & 1) + 6] = c | (c << 16);
+      }
+      // the accumulators to the new exponents, in exact steps of at most 2^120
+      while (dW != 0 || dB != 0) {
+        const int a = dW < -120 ? -120 : dW > 120 ? 120 : dW, b = dB < -120 ? -120 : dB > 120 ? 120 : dB;
+        const float fw = mfma::pow2_h(a), fb = li == K1 - 64 ? mfma::pow2_h(b) : fw;
+        // (one tile at a time: all 96 registers at once spilled the item loop's state)
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+          for (int u = 0; u < 3; u++) {
+            const float f = u == 2 ? fb : fw;
+#pragma unroll
+            for (int r = 0; r < 16; r++) g1[t][u][r] *= f;
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        dW -= a;
+        dB -= b;
+      }
+    }
     // ---- this sample's X pair images (buffer it & 1) ----
-    {
+    if constexpr (kD3) {
+      // (two fp16 parts of X 2^ex in dwords 0 and 1 of a position's three)
+      uint16_t* const x16 = reinterpret_cast<uint16_t*>(xi);
+#pragma unroll
+      for (int k = 0; k < kL12Regs; k++) {
+        const int i = threadIdx.x + 256 * k;
+        if (i < xn) {
+          const float xs = xr[k] * sX;
+          const _Float16 p0 = (_Float16)xs;
+          const _Float16 p[2] = {p0, (_Float16)(xs - (float)p0)};
+          const int y = i / W, x = i - y * W, ri = y * L.rs + x;
+          const int ti = L.rdw + 3 * ((x - x0col) * L.st + y);
+#pragma unroll
+          for (int q = 0; q < 2; q++) {
+            const uint16_t b = __builtin_bit_cast(uint16_t, p[q]);
+            x16[2 * (3 * ri + q)] = b;
+            if (ri > 0) x16[2 * (3 * (ri - 1) + q) + 1] = b;
+            if (L.tcols && x >= x0col) {
+              x16[2 * (ti + q)] = b;
+              if (y > 0) x16[2 * (ti - 3 + q) + 1] = b;
+            }
+          }
+        }
+      }
+    } else {
       uint16_t* const x16 = reinterpret_cast<uint16_t*>(xi);
 #pragma unroll
       for (int k = 0; k < kL12Regs; k++) {
@@ -631,13 +798,6 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
           }
         }
       }
-    }
-    if constexpr (kD3) {
-      // sample it + 1's delta3 image into buffer (it + 1) % 3, last read for
-      // sample it - 2 (every wave is past that sample: the barrier at the top
-      // of sample it - 1); read from the first delta2 of sample it + 1 on,
-      // after the barrier below
-      if (smp + (int)gridDim.x < g.batch) d3build((it + 1) - 3 * ((it + 1) / 3));
     }
     __syncthreads();  // images (and at it == 0 the tables) complete; buffer (it+1)&1 free
     const int nsmp = smp + (int)gridDim.x;
@@ -715,11 +875,15 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
 #pragma unroll
         for (int r = 0; r < 16; r++) d1[t][r] = a1r[t][r >> 2][r & 3] > 0.0f ? d1[t][r] : 0.0f;
       bf16x8 dx[2][2][3];  // delta1 parts [m][t]: m = 0 here, m = 1 under gW1's first half
+      mfma::f16x8 dxh[2][2][2];  // kD3: the two fp16 parts of delta1 2^e1
       auto split_d1 = [&](int m, int t) __attribute__((always_inline)) {
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = d1[t][8 * m + j];
-        d6_split(v, dx[m][t]);
+        for (int j = 0; j < 8; j++) v[j] = kD3 ? d1[t][8 * m + j] * s1 : d1[t][8 * m + j];  // (kD3: 2^e1, exact)
+        if constexpr (kD3)
+          mfma::split8_h(v, dxh[m][t]);
+        else
+          d6_split(v, dx[m][t]);
       };
       split_d1(0, 0);
       split_d1(0, 1);
@@ -767,8 +931,31 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
 #pragma unroll
         for (int q = 0; q < 3; q++) b[q] = __builtin_bit_cast(bf16x8, d[q]);
       };
+      // kD3: the two fp16 parts of X 2^ex (dwords 0 and 1 of a position's three)
+      const int spech = kD3 && li == K1 - 64 ? spec + 12 * (it & 1) : spec;
+      auto xread_h = [&](int m, int u, mfma::f16x8 (&b)[2]) __attribute__((always_inline)) {
+        u32x4 d[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+          int a = xrb[m][e] + (xrt[m][e] ? offT3[u] : offR3[u]);
+          if (u == 2) a = spech >= 0 ? spech : a;
+          int aq[2] = {a, a + 4};
+          asm("" : "+v"(aq[1]));
+#pragma unroll
+          for (int q = 0; q < 2; q++) {
+            d[q][2 * e] = *(lds_u32*)(uintptr_t)(unsigned)aq[q];
+            d[q][2 * e + 1] = *(lds_u32*)(uintptr_t)(unsigned)(aq[q] + 24);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 2; q++) b[q] = __builtin_bit_cast(mfma::f16x8, d[q]);
+      };
       bf16x8 bx[2][3];
-      xread(0, 0, bx[0]);
+      mfma::f16x8 bxh[2][2];
+      if constexpr (kD3)
+        xread_h(0, 0, bxh[0]);
+      else
+        xread(0, 0, bx[0]);
       f32x16 gacc[2];  // kD3: the next item's delta2 GEMM, two chains
       if constexpr (kD3) {
         // the next item's delta2 GEMM (12 MFMAs) as two fenced groups of 6,
@@ -808,11 +995,16 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
 #pragma unroll
       for (int st = 0; st < 6; st++) {
         const int m = st / 3, u = st % 3;
-        if (st < 5)
-          xread((st + 1) / 3, (st + 1) % 3, bx[(st + 1) & 1]);
-        else
+        if (st == 5)
           w2read0();  // the next item's phase A
-        mma_x6_2(dx[m][0], bx[st & 1], g1[0][u], dx[m][1], bx[st & 1], g1[1][u]);
+        else if constexpr (kD3)
+          xread_h((st + 1) / 3, (st + 1) % 3, bxh[(st + 1) & 1]);
+        else
+          xread((st + 1) / 3, (st + 1) % 3, bx[(st + 1) & 1]);
+        if constexpr (kD3)
+          mfma::mma_x3_h_2(dxh[m][0], bxh[st & 1], g1[0][u], dxh[m][1], bxh[st & 1], g1[1][u]);
+        else
+          mma_x6_2(dx[m][0], bx[st & 1], g1[0][u], dx[m][1], bx[st & 1], g1[1][u]);
         if (kTr) {
           // step 0: the delta2 sum and relu' mask, 1-2: da and its parts into
           // the image, 3: gB2's sums and the transposed reads of db
@@ -855,10 +1047,11 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
           split_d2(st - 1);  // 1-2 da, 3-4 db (+ gbs)
         }
 #pragma unroll
-        for (int i = 0; i < 12; i++) {
+        // (kD3: the same VALU and LDS work under half the MFMAs)
+        for (int i = 0; i < (kD3 ? 6 : 12); i++) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, kD3 ? 12 : 6, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, kD3 ? 2 : 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -866,6 +1059,7 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       kj = nj;
       kc = nc;
     }
+    m3cur = m3next;
   }
   SRCNN_CLOCK_END(g_clk, 2);
 
@@ -911,6 +1105,19 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       }
       if (tile < 6) {
         const int t = tile / 3, u = tile % 3, tap = 32 * u + li;
+        if constexpr (kD3) {
+          // the sums leave their scale 2^EW (the bias column 2^EB), in three
+          // exact steps (|EW| <= 378); every wave holds the same exponents
+          int e = -(tap == K1 ? EB : EW);
+#pragma unroll
+          for (int k = 0; k < 3; k++) {
+            const int a = e < -126 ? -126 : e > 126 ? 126 : e;
+            const float f = mfma::pow2_h(a);
+#pragma unroll
+            for (int r = 0; r < 16; r++) sum[r] *= f;
+            e -= a;
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 16; r++)
           if (tap <= K1) stg_w1(tap, 32 * t + crow(r, h)) = sum[r];  // (tap K1: gB1, row 81 at NW1)
