@@ -158,6 +158,101 @@ int planes_dims(const char* who, uint32_t src_pitch, uint32_t pw, uint32_t ph, u
   return SRCNN_OK;
 }
 
+// The three Y'CbCr operations, each behind its 8-bit entry point (bits 8,
+// msb 0, planar) and its general one; `who` is the one the caller used.
+int yuv_upscale_luma(const char* who, const void* y, uint32_t pitch_y, float* luma_padded,
+                     uint32_t w, uint32_t h, uint32_t scale, uint32_t pad, uint32_t bits,
+                     uint32_t msb, int range, srcnn_stream_t stream) {
+  UpDims d;
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = yuv_luma_dims(who, w, h, pitch_y, scale, pad, &d, B)) return rc;
+  if (int rc = yuv_range(who, range)) return rc;
+  SRCNN_REQUIRE(y && luma_padded, "%s: null buffer", who);
+  SRCNN_REQUIRE(!odd_address(B, y), "%s: odd address of two-byte samples", who);
+  return srcnn::yuv_upscale_luma(y, pitch_y, luma_padded, w, h, scale, pad, bits, msb != 0,
+                                 range == SRCNN_YUV_FULL, as_stream(stream));
+}
+int yuv_compose_luma(const char* who, const float* luma, void* y, uint32_t pitch_y, uint32_t W,
+                     uint32_t H, uint32_t bits, uint32_t msb, int range, srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = plane_dims(who, W, H, pitch_y, B)) return rc;
+  if (int rc = yuv_range(who, range)) return rc;
+  SRCNN_REQUIRE(luma && y, "%s: null buffer", who);
+  SRCNN_REQUIRE(!odd_address(B, y), "%s: odd address of two-byte samples", who);
+  return srcnn::yuv_compose_luma(luma, y, pitch_y, W, H, bits, msb != 0, range == SRCNN_YUV_FULL,
+                                 as_stream(stream));
+}
+int yuv_layout(const char* who, uint32_t layout) {
+  SRCNN_REQUIRE(layout == SRCNN_YUV_PLANAR || layout == SRCNN_YUV_SEMIPLANAR,
+                "%s: layout %u is neither SRCNN_YUV_PLANAR nor SRCNN_YUV_SEMIPLANAR", who, layout);
+  return SRCNN_OK;
+}
+int upscale_planes(const char* who, const void* src0, const void* src1, uint32_t src_pitch,
+                   uint32_t pw, uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch,
+                   uint32_t ow, uint32_t oh, uint32_t scale, uint32_t bits, uint32_t msb,
+                   uint32_t layout, srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = yuv_layout(who, layout)) return rc;
+  const bool semi = layout == SRCNN_YUV_SEMIPLANAR;
+  if (int rc = planes_dims(who, src_pitch, pw, ph, dst_pitch, ow, oh, scale, B, semi ? 2 : 1))
+    return rc;
+  SRCNN_REQUIRE(src0 && dst0, "%s: null buffer", who);
+  if (semi) {
+    SRCNN_REQUIRE(!src1 && !dst1, "%s: a semi-planar frame has no second chroma plane", who);
+  } else {
+    SRCNN_REQUIRE(src1 && dst1, "%s: null buffer", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, src0) && !odd_address(B, src1) && !odd_address(B, dst0) &&
+                    !odd_address(B, dst1),
+                "%s: odd address of two-byte samples", who);
+  return srcnn::upscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
+                               bits, msb != 0, semi, as_stream(stream));
+}
+
+// regions of the upscale workspace: padded plane | net output | reduction
+// scratch | forward workspace, each 256-byte aligned
+struct UpWs {
+  size_t plane, out, red, fwd, total;  // byte offsets of the regions, and their sum
+  size_t red_bytes, fwd_bytes;         // what the reduction and the forward are given
+};
+bool up_ws(const srcnn_net* net, const UpDims& d, UpWs* L) {
+  L->fwd_bytes = srcnn_forward_workspace_bytes(net, d.PW, d.PH, 1);
+  if (L->fwd_bytes == 0) return false;
+  const size_t plane = (size_t)d.PW * d.PH;
+  L->red_bytes = srcnn_reduce_workspace_bytes(plane);
+  L->plane = 0;
+  L->out = L->plane + align_up(plane * sizeof(float));
+  L->red = L->out + align_up((size_t)d.W * d.H * sizeof(float));
+  L->fwd = L->red + align_up(L->red_bytes);
+  L->total = L->fwd + align_up(L->fwd_bytes);
+  return true;
+}
+// What srcnn_upscale, srcnn_upscale_yuv and srcnn_upscale_frame (`who`) do
+// between their checks and their composition: the workspace carved and
+// measured, fill_plane(plane) for the padded bicubic luma, then the plane
+// minus its mean through the net.  *luma: the net's output [H][W], in ws.
+template <typename FillPlane>
+int up_net(const char* who, const srcnn_net* net, const UpDims& d, const float* params, void* ws,
+           size_t ws_bytes, srcnn_stream_t stream, FillPlane fill_plane, float** luma) {
+  UpWs L;
+  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
+  if (ws_bytes < L.total)
+    return fail(SRCNN_ERR_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  *luma = reinterpret_cast<float*>(p + L.out);
+  int rc;
+  if ((rc = fill_plane(plane))) return rc;
+  // the mean of what the net sees: the whole padded plane; not added back
+  // (the reference flow: cnn.cpp subtracts it and pastes the net's output)
+  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
+    return rc;
+  return srcnn_forward(net, plane, d.PW, d.PH, 1, params, *luma, p + L.fwd, L.fwd_bytes, stream);
+}
+
 // srcnn_downscale_rgba / srcnn_make_pairs: the source against the scale and
 // against what downscale_rgba_kernel can index (pixel offsets below 2^31)
 int down_dims(const char* who, uint32_t W, uint32_t H, uint32_t scale) {
@@ -434,84 +529,41 @@ int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* r
 int srcnn_yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
                            uint32_t h, uint32_t scale, uint32_t pad, int range,
                            srcnn_stream_t stream) {
-  UpDims d;
-  if (int rc = yuv_luma_dims("yuv_upscale_luma", w, h, pitch_y, scale, pad, &d)) return rc;
-  if (int rc = yuv_range("yuv_upscale_luma", range)) return rc;
-  SRCNN_REQUIRE(y && luma_padded, "yuv_upscale_luma: null buffer");
-  return srcnn::yuv_upscale_luma(y, pitch_y, luma_padded, w, h, scale, pad, range == SRCNN_YUV_FULL,
-                                 as_stream(stream));
+  return yuv_upscale_luma("yuv_upscale_luma", y, pitch_y, luma_padded, w, h, scale, pad, 8, 0, range,
+                          stream);
 }
 
 int srcnn_upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch,
                             uint32_t pw, uint32_t ph, uint8_t* dst0, uint8_t* dst1,
                             uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t scale,
                             srcnn_stream_t stream) {
-  if (int rc = planes_dims("upscale_planes_u8", src_pitch, pw, ph, dst_pitch, ow, oh, scale))
-    return rc;
-  SRCNN_REQUIRE(src0 && src1 && dst0 && dst1, "upscale_planes_u8: null buffer");
-  return srcnn::upscale_planes_u8(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh,
-                                  scale, as_stream(stream));
+  return upscale_planes("upscale_planes_u8", src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow,
+                        oh, scale, 8, 0, SRCNN_YUV_PLANAR, stream);
 }
 
 int srcnn_yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
                            int range, srcnn_stream_t stream) {
-  if (int rc = plane_dims("yuv_compose_luma", W, H, pitch_y)) return rc;
-  if (int rc = yuv_range("yuv_compose_luma", range)) return rc;
-  SRCNN_REQUIRE(luma && y, "yuv_compose_luma: null buffer");
-  return srcnn::yuv_compose_luma(luma, y, pitch_y, W, H, range == SRCNN_YUV_FULL,
-                                 as_stream(stream));
+  return yuv_compose_luma("yuv_compose_luma", luma, y, pitch_y, W, H, 8, 0, range, stream);
 }
 
 int srcnn_yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
                              uint32_t h, uint32_t scale, uint32_t pad, uint32_t bits, uint32_t msb,
                              int range, srcnn_stream_t stream) {
-  UpDims d;
-  uint32_t B;
-  if (int rc = yuv_samples("yuv_upscale_luma16", bits, msb, &B)) return rc;
-  if (int rc = yuv_luma_dims("yuv_upscale_luma16", w, h, pitch_y, scale, pad, &d, B)) return rc;
-  if (int rc = yuv_range("yuv_upscale_luma16", range)) return rc;
-  SRCNN_REQUIRE(y && luma_padded, "yuv_upscale_luma16: null buffer");
-  SRCNN_REQUIRE(!odd_address(B, y), "yuv_upscale_luma16: odd address of two-byte samples");
-  return srcnn::yuv_upscale_luma16(y, pitch_y, luma_padded, w, h, scale, pad, bits, msb != 0,
-                                   range == SRCNN_YUV_FULL, as_stream(stream));
+  return yuv_upscale_luma("yuv_upscale_luma16", y, pitch_y, luma_padded, w, h, scale, pad, bits, msb,
+                          range, stream);
 }
 
 int srcnn_yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
                              uint32_t bits, uint32_t msb, int range, srcnn_stream_t stream) {
-  uint32_t B;
-  if (int rc = yuv_samples("yuv_compose_luma16", bits, msb, &B)) return rc;
-  if (int rc = plane_dims("yuv_compose_luma16", W, H, pitch_y, B)) return rc;
-  if (int rc = yuv_range("yuv_compose_luma16", range)) return rc;
-  SRCNN_REQUIRE(luma && y, "yuv_compose_luma16: null buffer");
-  SRCNN_REQUIRE(!odd_address(B, y), "yuv_compose_luma16: odd address of two-byte samples");
-  return srcnn::yuv_compose_luma16(luma, y, pitch_y, W, H, bits, msb != 0, range == SRCNN_YUV_FULL,
-                                   as_stream(stream));
+  return yuv_compose_luma("yuv_compose_luma16", luma, y, pitch_y, W, H, bits, msb, range, stream);
 }
 
 int srcnn_upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
                          uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow,
                          uint32_t oh, uint32_t scale, uint32_t bits, uint32_t msb, uint32_t layout,
                          srcnn_stream_t stream) {
-  uint32_t B;
-  if (int rc = yuv_samples("upscale_planes", bits, msb, &B)) return rc;
-  SRCNN_REQUIRE(layout == SRCNN_YUV_PLANAR || layout == SRCNN_YUV_SEMIPLANAR,
-                "upscale_planes: layout %u is neither SRCNN_YUV_PLANAR nor SRCNN_YUV_SEMIPLANAR",
-                layout);
-  const bool semi = layout == SRCNN_YUV_SEMIPLANAR;
-  if (int rc = planes_dims("upscale_planes", src_pitch, pw, ph, dst_pitch, ow, oh, scale, B,
-                           semi ? 2 : 1))
-    return rc;
-  SRCNN_REQUIRE(src0 && dst0, "upscale_planes: null buffer");
-  if (semi) {
-    SRCNN_REQUIRE(!src1 && !dst1, "upscale_planes: a semi-planar frame has no second chroma plane");
-  } else {
-    SRCNN_REQUIRE(src1 && dst1, "upscale_planes: null buffer");
-  }
-  SRCNN_REQUIRE(!odd_address(B, src0) && !odd_address(B, src1) && !odd_address(B, dst0) &&
-                    !odd_address(B, dst1),
-                "upscale_planes: odd address of two-byte samples");
-  return srcnn::upscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
-                               bits, msb != 0, semi, as_stream(stream));
+  return upscale_planes("upscale_planes", src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh,
+                        scale, bits, msb, layout, stream);
 }
 
 int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
@@ -930,25 +982,6 @@ int srcnn_forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, 
   return seq.done(srcnn_conv_fwd(A2, out, P.W3, P.B3, d.w2, d.h2, net->n2, 1, net->f3, 0, batch, stream));
 }
 
-// regions of the upscale workspace: padded plane | net output | reduction
-// scratch | forward workspace, each 256-byte aligned
-struct UpWs {
-  size_t plane, out, red, fwd, total;  // byte offsets of the regions, and their sum
-  size_t red_bytes, fwd_bytes;         // what the reduction and the forward are given
-};
-static bool up_ws(const srcnn_net* net, const UpDims& d, UpWs* L) {
-  L->fwd_bytes = srcnn_forward_workspace_bytes(net, d.PW, d.PH, 1);
-  if (L->fwd_bytes == 0) return false;
-  const size_t plane = (size_t)d.PW * d.PH;
-  L->red_bytes = srcnn_reduce_workspace_bytes(plane);
-  L->plane = 0;
-  L->out = L->plane + align_up(plane * sizeof(float));
-  L->red = L->out + align_up((size_t)d.W * d.H * sizeof(float));
-  L->fwd = L->red + align_up(L->red_bytes);
-  L->total = L->fwd + align_up(L->fwd_bytes);
-  return true;
-}
-
 size_t srcnn_upscale_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
                                      uint32_t scale) {
   size_t off[6];
@@ -971,21 +1004,11 @@ int srcnn_upscale(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_
   UpDims d;
   if (int rc = up_dims("upscale", w, h, scale, pad, &d)) return rc;
   SRCNN_REQUIRE(rgba && params && rgb && ws, "upscale: null buffer");
-  UpWs L;
-  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
-  if (ws_bytes < L.total)
-    return fail(SRCNN_ERR_WORKSPACE, "upscale: workspace %zu B < %zu B", ws_bytes, L.total);
-  char* p = static_cast<char*>(ws);
-  float* plane = reinterpret_cast<float*>(p + L.plane);
-  float* out = reinterpret_cast<float*>(p + L.out);
-  int rc;
-  if ((rc = srcnn_upscale_luma(rgba, plane, w, h, scale, pad, stream))) return rc;
-  // the mean of what the net sees: the whole padded plane; not added back
-  // (the reference flow: cnn.cpp subtracts it and pastes the net's output)
-  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
-    return rc;
-  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
-    return rc;
+  float* out;
+  const auto luma = [&](float* plane) {
+    return srcnn_upscale_luma(rgba, plane, w, h, scale, pad, stream);
+  };
+  if (int rc = up_net("upscale", net, d, params, ws, ws_bytes, stream, luma, &out)) return rc;
   return srcnn_upscale_compose(rgba, out, rgb, w, h, scale, stream);
 }
 
@@ -1023,38 +1046,53 @@ size_t srcnn_upscale_yuv_workspace_bytes(const srcnn_net* net, uint32_t w, uint3
   return up_ws(net, y.d, &L) ? L.total : 0;
 }
 
+// srcnn_upscale_yuv (8 bits, planar) and srcnn_upscale_frame: `who`
+static int upscale_frame(const char* who, const srcnn_net* net, const srcnn_yuv_format& fmt,
+                         const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst, uint32_t w,
+                         uint32_t h, uint32_t scale, const float* params, void* ws, size_t ws_bytes,
+                         srcnn_stream_t stream) {
+  YuvDims y;
+  uint32_t B;
+  if (int rc = yuv_dims(who, net, w, h, fmt.cx, fmt.cy, scale, &y)) return rc;
+  if (int rc = yuv_range(who, fmt.range)) return rc;
+  if (int rc = yuv_samples(who, fmt.bits, fmt.msb, &B)) return rc;
+  if (int rc = yuv_layout(who, fmt.layout)) return rc;
+  const bool semi = fmt.layout == SRCNN_YUV_SEMIPLANAR;
+  SRCNN_REQUIRE(src && dst && params && ws, "%s: null buffer", who);
+  SRCNN_REQUIRE(src->y && src->u && dst->y && dst->u, "%s: null plane", who);
+  if (semi) {
+    SRCNN_REQUIRE(!src->v && !dst->v, "%s: a semi-planar frame has no v plane", who);
+  } else {
+    SRCNN_REQUIRE(src->v && dst->v, "%s: null plane", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, src->y) && !odd_address(B, src->u) && !odd_address(B, src->v) &&
+                    !odd_address(B, dst->y) && !odd_address(B, dst->u) && !odd_address(B, dst->v),
+                "%s: odd address of two-byte samples", who);
+  // (the sizes again, now with the frames' pitches)
+  UpDims d;
+  if (int rc = yuv_luma_dims(who, w, h, src->pitch_y, scale, y.pad, &d, B)) return rc;
+  if (int rc = plane_dims(who, d.W, d.H, dst->pitch_y, B)) return rc;
+  if (int rc = planes_dims(who, src->pitch_c, y.cw, y.ch, dst->pitch_c, y.CW, y.CH, scale, B,
+                           semi ? 2 : 1))
+    return rc;
+  float* out;
+  const auto luma = [&](float* plane) {
+    return yuv_upscale_luma(who, src->y, src->pitch_y, plane, w, h, scale, y.pad, fmt.bits, fmt.msb,
+                            fmt.range, stream);
+  };
+  if (int rc = up_net(who, net, d, params, ws, ws_bytes, stream, luma, &out)) return rc;
+  if (int rc = yuv_compose_luma(who, out, dst->y, dst->pitch_y, d.W, d.H, fmt.bits, fmt.msb,
+                                fmt.range, stream))
+    return rc;
+  return upscale_planes(who, src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v, dst->pitch_c,
+                        y.CW, y.CH, scale, fmt.bits, fmt.msb, fmt.layout, stream);
+}
+
 int srcnn_upscale_yuv(const srcnn_net* net, const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst,
                       uint32_t w, uint32_t h, uint32_t cx, uint32_t cy, uint32_t scale, int range,
                       const float* params, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
-  YuvDims y;
-  if (int rc = yuv_dims("upscale_yuv", net, w, h, cx, cy, scale, &y)) return rc;
-  if (int rc = yuv_range("upscale_yuv", range)) return rc;
-  SRCNN_REQUIRE(src && dst && params && ws, "upscale_yuv: null buffer");
-  SRCNN_REQUIRE(src->y && src->u && src->v && dst->y && dst->u && dst->v,
-                "upscale_yuv: null plane");
-  // (the sizes again, now with the frames' pitches)
-  UpDims d;
-  if (int rc = yuv_luma_dims("upscale_yuv", w, h, src->pitch_y, scale, y.pad, &d)) return rc;
-  if (int rc = plane_dims("upscale_yuv", d.W, d.H, dst->pitch_y)) return rc;
-  if (int rc = planes_dims("upscale_yuv", src->pitch_c, y.cw, y.ch, dst->pitch_c, y.CW, y.CH, scale))
-    return rc;
-  UpWs L;
-  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
-  if (ws_bytes < L.total)
-    return fail(SRCNN_ERR_WORKSPACE, "upscale_yuv: workspace %zu B < %zu B", ws_bytes, L.total);
-  char* p = static_cast<char*>(ws);
-  float* plane = reinterpret_cast<float*>(p + L.plane);
-  float* out = reinterpret_cast<float*>(p + L.out);
-  int rc;
-  if ((rc = srcnn_yuv_upscale_luma(src->y, src->pitch_y, plane, w, h, scale, y.pad, range, stream)))
-    return rc;
-  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
-    return rc;
-  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
-    return rc;
-  if ((rc = srcnn_yuv_compose_luma(out, dst->y, dst->pitch_y, d.W, d.H, range, stream))) return rc;
-  return srcnn_upscale_planes_u8(src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v,
-                                 dst->pitch_c, y.CW, y.CH, scale, stream);
+  const srcnn_yuv_format fmt{8, 0, SRCNN_YUV_PLANAR, cx, cy, range};
+  return upscale_frame("upscale_yuv", net, fmt, src, dst, w, h, scale, params, ws, ws_bytes, stream);
 }
 
 int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
@@ -1062,53 +1100,8 @@ int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
                         uint32_t h, uint32_t scale, const float* params, void* ws, size_t ws_bytes,
                         srcnn_stream_t stream) {
   SRCNN_REQUIRE(fmt, "upscale_frame: null srcnn_yuv_format");
-  YuvDims y;
-  uint32_t B;
-  if (int rc = yuv_dims("upscale_frame", net, w, h, fmt->cx, fmt->cy, scale, &y)) return rc;
-  if (int rc = yuv_range("upscale_frame", fmt->range)) return rc;
-  if (int rc = yuv_samples("upscale_frame", fmt->bits, fmt->msb, &B)) return rc;
-  SRCNN_REQUIRE(fmt->layout == SRCNN_YUV_PLANAR || fmt->layout == SRCNN_YUV_SEMIPLANAR,
-                "upscale_frame: layout %u is neither SRCNN_YUV_PLANAR nor SRCNN_YUV_SEMIPLANAR",
-                fmt->layout);
-  const bool semi = fmt->layout == SRCNN_YUV_SEMIPLANAR;
-  SRCNN_REQUIRE(src && dst && params && ws, "upscale_frame: null buffer");
-  SRCNN_REQUIRE(src->y && src->u && dst->y && dst->u, "upscale_frame: null plane");
-  if (semi) {
-    SRCNN_REQUIRE(!src->v && !dst->v, "upscale_frame: a semi-planar frame has no v plane");
-  } else {
-    SRCNN_REQUIRE(src->v && dst->v, "upscale_frame: null plane");
-  }
-  SRCNN_REQUIRE(!odd_address(B, src->y) && !odd_address(B, src->u) && !odd_address(B, src->v) &&
-                    !odd_address(B, dst->y) && !odd_address(B, dst->u) && !odd_address(B, dst->v),
-                "upscale_frame: odd address of two-byte samples");
-  // (the sizes again, now with the frames' pitches)
-  UpDims d;
-  if (int rc = yuv_luma_dims("upscale_frame", w, h, src->pitch_y, scale, y.pad, &d, B)) return rc;
-  if (int rc = plane_dims("upscale_frame", d.W, d.H, dst->pitch_y, B)) return rc;
-  if (int rc = planes_dims("upscale_frame", src->pitch_c, y.cw, y.ch, dst->pitch_c, y.CW, y.CH,
-                           scale, B, semi ? 2 : 1))
-    return rc;
-  UpWs L;
-  if (!up_ws(net, d, &L)) return SRCNN_ERR_INVALID;  // (message from net_dims)
-  if (ws_bytes < L.total)
-    return fail(SRCNN_ERR_WORKSPACE, "upscale_frame: workspace %zu B < %zu B", ws_bytes, L.total);
-  char* p = static_cast<char*>(ws);
-  float* plane = reinterpret_cast<float*>(p + L.plane);
-  float* out = reinterpret_cast<float*>(p + L.out);
-  int rc;
-  if ((rc = srcnn_yuv_upscale_luma16(src->y, src->pitch_y, plane, w, h, scale, y.pad, fmt->bits,
-                                     fmt->msb, fmt->range, stream)))
-    return rc;
-  if ((rc = srcnn_sub_mean(plane, (size_t)d.PW * d.PH, nullptr, p + L.red, L.red_bytes, stream)))
-    return rc;
-  if ((rc = srcnn_forward(net, plane, d.PW, d.PH, 1, params, out, p + L.fwd, L.fwd_bytes, stream)))
-    return rc;
-  if ((rc = srcnn_yuv_compose_luma16(out, dst->y, dst->pitch_y, d.W, d.H, fmt->bits, fmt->msb,
-                                     fmt->range, stream)))
-    return rc;
-  return srcnn_upscale_planes(src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v,
-                              dst->pitch_c, y.CW, y.CH, scale, fmt->bits, fmt->msb, fmt->layout,
-                              stream);
+  return upscale_frame("upscale_frame", net, *fmt, src, dst, w, h, scale, params, ws, ws_bytes,
+                       stream);
 }
 
 // regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |

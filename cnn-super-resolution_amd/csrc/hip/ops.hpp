@@ -251,30 +251,22 @@ int upscale_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint
 int upscale_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
                     uint32_t scale, hipStream_t s);
 int preload_upscale();
-// yuv.hip: the same resampling for planar Y'CbCr frames: the Y
-// plane [h][w] u8 (pitch in bytes) into the padded plane as upscale_luma does,
-// normalised by the range; two u8 planes [ph][pw] bicubic x scale, rounded and
-// clamped, the top-left ow x oh of each into two u8 planes; the net's luma
-// [H][W] back into a Y plane
-int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
-                     uint32_t scale, uint32_t pad, bool full_range, hipStream_t s);
-int upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
-                      uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
-                      uint32_t oh, uint32_t scale, hipStream_t s);
-int yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
-                     bool full_range, hipStream_t s);
-// the same three for every sample format of DESIGN.md 15: `bits` 8..16, one
-// byte per sample at 8 bits (then they are the calls above), else a 16-bit
-// word with the value in its low (msb false) or high bits; pitches in bytes;
-// semiplanar: src0 / dst0 hold (U, V) pairs [ph][pw][2], src1 / dst1 unused
-int yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
-                       uint32_t scale, uint32_t pad, uint32_t bits, bool msb, bool full_range,
-                       hipStream_t s);
+// yuv.hip: the same resampling for Y'CbCr frames: the Y
+// plane [h][w] into the padded plane as upscale_luma does, normalised by the
+// range; a frame's chroma [ph][pw] bicubic x scale, rounded and clamped, the
+// top-left ow x oh of it in the same layout; the net's luma [H][W] back into
+// a Y plane.  A sample has `bits` bits, 8..16: one byte at 8 bits, else a
+// 16-bit word with the value in its low (msb false) or high bits; pitches in
+// bytes; semiplanar: src0 / dst0 hold (U, V) pairs [ph][pw][2], src1 / dst1
+// unused, else two planes each way
+int yuv_upscale_luma(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                     uint32_t scale, uint32_t pad, uint32_t bits, bool msb, bool full_range,
+                     hipStream_t s);
 int upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw, uint32_t ph,
                    void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
                    uint32_t scale, uint32_t bits, bool msb, bool semiplanar, hipStream_t s);
-int yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
-                       uint32_t bits, bool msb, bool full_range, hipStream_t s);
+int yuv_compose_luma(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                     uint32_t bits, bool msb, bool full_range, hipStream_t s);
 int preload_yuv();
 // pairs.hip: antialiased bicubic / scale (1..4) of rgba [H][W][4] into small
 // [H/scale][W/scale][4], and the cut of a grid of nx x ny tiles (tw x th,

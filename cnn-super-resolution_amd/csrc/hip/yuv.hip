@@ -299,16 +299,17 @@ int launch_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, ui
   return SRCNN_OK;
 }
 
-template <int B, int NCH>
+template <int B>
 int launch_planes(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
                   uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
-                  uint32_t oh, uint32_t scale, Fmt<B> f, hipStream_t s) {
+                  uint32_t oh, uint32_t scale, bool semiplanar, Fmt<B> f, hipStream_t s) {
 #define SRCNN_YUV_PLANES(S)                                                                       \
   {                                                                                               \
     const uint32_t tx = tiles(pw, Tile<S, true>::JX), ty = tiles(ph, Tile<S, true>::JY);          \
-    hipLaunchKernelGGL((upscale_planes_kernel<S, B, NCH>), dim3(tx* ty, NCH == 1 ? 2 : 1),        \
-                       dim3(kThreads), 0, s, src0, src1, (size_t)src_pitch, (int)pw, (int)ph,     \
-                       dst0, dst1, (size_t)dst_pitch, (int)ow, (int)oh, (int)tx, f);              \
+    const auto k = semiplanar ? upscale_planes_kernel<S, B, 2> : upscale_planes_kernel<S, B, 1>;  \
+    hipLaunchKernelGGL(k, dim3(tx* ty, semiplanar ? 1 : 2), dim3(kThreads), 0, s, src0, src1,     \
+                       (size_t)src_pitch, (int)pw, (int)ph, dst0, dst1, (size_t)dst_pitch,        \
+                       (int)ow, (int)oh, (int)tx, f);                                             \
   }
   switch (scale) {
     case 1: SRCNN_YUV_PLANES(1); break;
@@ -322,73 +323,59 @@ int launch_planes(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, 
   return SRCNN_OK;
 }
 
+// SRCNN_PROFILE's label of a call: what was there before the deeper formats
+//  keeps the name it was first measured under
+const char* label(bool first, const char* name8, const char* name) { return first ? name8 : name; }
+
+// the range of a Y sample of `bits` bits: Y = off + span * luma, with
+// (off, span) = (16, 219) times up = 2^(bits-8) for limited range, exactly the
+// 8-bit pair at 8 bits, and (0, 2^bits - 1) for full range
+struct Range {
+  float off, span;
+};
+Range range_of(uint32_t bits, bool full_range) {
+  const float up = (float)(1u << (bits - 8));  // exact
+  return full_range ? Range{0.0f, (float)((1u << bits) - 1u)} : Range{16.0f * up, 219.0f * up};
+}
+
 }  // namespace
 
-int yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
-                     uint32_t scale, uint32_t pad, bool full_range, hipStream_t s) {
-  SRCNN_PROFILE("yuv_upscale_luma", s);
-  const float off = full_range ? 0.0f : 16.0f, div = full_range ? 255.0f : 219.0f;
-  return launch_luma<1>(y, pitch_y, plane, w, h, scale, pad, off, div, Fmt<1>{}, s);
-}
-
-int yuv_upscale_luma16(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
-                       uint32_t scale, uint32_t pad, uint32_t bits, bool msb, bool full_range,
-                       hipStream_t s) {
-  if (bits == 8) return yuv_upscale_luma(static_cast<const uint8_t*>(y), pitch_y, plane, w, h, scale, pad, full_range, s);
-  SRCNN_PROFILE("yuv_upscale_luma16", s);
-  const float up = (float)(1u << (bits - 8));  // exact
-  const float off = full_range ? 0.0f : 16.0f * up;
-  const float div = full_range ? (float)((1u << bits) - 1u) : 219.0f * up;
-  return launch_luma<2>(static_cast<const uint8_t*>(y), pitch_y, plane, w, h, scale, pad, off, div,
-                        deep_fmt(bits, msb), s);
-}
-
-int upscale_planes_u8(const uint8_t* src0, const uint8_t* src1, uint32_t src_pitch, uint32_t pw,
-                      uint32_t ph, uint8_t* dst0, uint8_t* dst1, uint32_t dst_pitch, uint32_t ow,
-                      uint32_t oh, uint32_t scale, hipStream_t s) {
-  SRCNN_PROFILE("upscale_planes_u8", s);
-  return launch_planes<1, 1>(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
-                             Fmt<1>{}, s);
+int yuv_upscale_luma(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h,
+                     uint32_t scale, uint32_t pad, uint32_t bits, bool msb, bool full_range,
+                     hipStream_t s) {
+  SRCNN_PROFILE(label(bits == 8, "yuv_upscale_luma", "yuv_upscale_luma16"), s);
+  const uint8_t* src = static_cast<const uint8_t*>(y);
+  const Range r = range_of(bits, full_range);
+  if (bits == 8)
+    return launch_luma<1>(src, pitch_y, plane, w, h, scale, pad, r.off, r.span, Fmt<1>{}, s);
+  return launch_luma<2>(src, pitch_y, plane, w, h, scale, pad, r.off, r.span, deep_fmt(bits, msb),
+                        s);
 }
 
 int upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw, uint32_t ph,
                    void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
                    uint32_t scale, uint32_t bits, bool msb, bool semiplanar, hipStream_t s) {
+  SRCNN_PROFILE(label(bits == 8 && !semiplanar, "upscale_planes_u8", "upscale_planes"), s);
   const uint8_t *a = static_cast<const uint8_t*>(src0), *b = static_cast<const uint8_t*>(src1);
   uint8_t *A = static_cast<uint8_t*>(dst0), *Bp = static_cast<uint8_t*>(dst1);
-  if (bits == 8 && !semiplanar)
-    return upscale_planes_u8(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, s);
-  SRCNN_PROFILE("upscale_planes", s);
   if (bits == 8)
-    return launch_planes<1, 2>(a, nullptr, src_pitch, pw, ph, A, nullptr, dst_pitch, ow, oh, scale,
-                               Fmt<1>{}, s);
-  const Fmt<2> f = deep_fmt(bits, msb);
-  if (semiplanar)
-    return launch_planes<2, 2>(a, nullptr, src_pitch, pw, ph, A, nullptr, dst_pitch, ow, oh, scale,
-                               f, s);
-  return launch_planes<2, 1>(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, f, s);
+    return launch_planes<1>(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, semiplanar,
+                            Fmt<1>{}, s);
+  return launch_planes<2>(a, b, src_pitch, pw, ph, A, Bp, dst_pitch, ow, oh, scale, semiplanar,
+                          deep_fmt(bits, msb), s);
 }
 
-int yuv_compose_luma(const float* luma, uint8_t* y, uint32_t pitch_y, uint32_t W, uint32_t H,
-                     bool full_range, hipStream_t s) {
-  SRCNN_PROFILE("yuv_compose_luma", s);
-  const float mul = full_range ? 255.0f : 219.0f, add = full_range ? 0.0f : 16.0f;
-  hipLaunchKernelGGL(yuv_compose_luma_kernel<1>, dim3(tiles(H, kThreads / 64)), dim3(kThreads), 0,
-                     s, luma, y, (size_t)pitch_y, (int)W, (int)H, mul, add, Fmt<1>{});
-  SRCNN_LAUNCH_TRY();
-  return SRCNN_OK;
-}
-
-int yuv_compose_luma16(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
-                       uint32_t bits, bool msb, bool full_range, hipStream_t s) {
-  if (bits == 8) return yuv_compose_luma(luma, static_cast<uint8_t*>(y), pitch_y, W, H, full_range, s);
-  SRCNN_PROFILE("yuv_compose_luma16", s);
-  const float up = (float)(1u << (bits - 8));  // exact
-  const float mul = full_range ? (float)((1u << bits) - 1u) : 219.0f * up;
-  const float add = full_range ? 0.0f : 16.0f * up;
-  hipLaunchKernelGGL(yuv_compose_luma_kernel<2>, dim3(H), dim3(kThreads), 0,
-                     s, luma, static_cast<uint8_t*>(y), (size_t)pitch_y, (int)W, (int)H, mul, add,
-                     deep_fmt(bits, msb));
+int yuv_compose_luma(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
+                     uint32_t bits, bool msb, bool full_range, hipStream_t s) {
+  SRCNN_PROFILE(label(bits == 8, "yuv_compose_luma", "yuv_compose_luma16"), s);
+  uint8_t* dst = static_cast<uint8_t*>(y);
+  const Range r = range_of(bits, full_range);
+  if (bits == 8)
+    hipLaunchKernelGGL(yuv_compose_luma_kernel<1>, dim3(tiles(H, kThreads / 64)), dim3(kThreads), 0,
+                       s, luma, dst, (size_t)pitch_y, (int)W, (int)H, r.span, r.off, Fmt<1>{});
+  else
+    hipLaunchKernelGGL(yuv_compose_luma_kernel<2>, dim3(H), dim3(kThreads), 0, s, luma, dst,
+                       (size_t)pitch_y, (int)W, (int)H, r.span, r.off, deep_fmt(bits, msb));
   SRCNN_LAUNCH_TRY();
   return SRCNN_OK;
 }

@@ -35,6 +35,12 @@ srcnn_net ConfigBasedDataPipeline::net() const {
   return n;
 }
 
+std::string ConfigBasedDataPipeline::net_defines() const {
+  return "-D N1=" + std::to_string(_config->n1) + " -D N2=" + std::to_string(_config->n2) +
+         " -D F1=" + std::to_string(_config->f1) + " -D F2=" + std::to_string(_config->f2) +
+         " -D F3=" + std::to_string(_config->f3);
+}
+
 void ConfigBasedDataPipeline::init(int load_flags) {
   DataPipeline::init(load_flags);
   if (!_config->parameters_file.empty()) {
@@ -58,10 +64,7 @@ void ConfigBasedDataPipeline::load_kernels(int load_flags) {
   DataPipeline::load_kernels(load_flags);
   using srcnn::KernelKind;
   // net-level launches carry the net shape as their defines
-  const std::string net_args = "-D N1=" + std::to_string(_config->n1) + " -D N2=" +
-                               std::to_string(_config->n2) + " -D F1=" + std::to_string(_config->f1) +
-                               " -D F2=" + std::to_string(_config->f2) + " -D F3=" +
-                               std::to_string(_config->f3);
+  const std::string net_args = net_defines();
   if ((load_flags & LOAD_KERNEL_LAYERS) && !_layer_1_kernel) {
     _layer_1_kernel = create_layer_kernel(layer_data_1, false);
     _layer_2_kernel = create_layer_kernel(layer_data_2, false);
@@ -236,12 +239,8 @@ void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, 
   _context->write_image(rgba, low_res, true);
   MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, W * H * 3);
   void* wsp = scratch(ws);
-  if (!_upscale_kernel) {
-    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
-                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
-                             " -D F3=" + std::to_string(nt.f3);
-    _upscale_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale", 0, 0, 0, false, args);
-  }
+  if (!_upscale_kernel)
+    _upscale_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale", 0, 0, 0, false, net_defines());
   {
     srcnn::Context::Launch l(*_context, *_upscale_kernel);
     check(srcnn_upscale(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), low_res.w, low_res.h, scale,
@@ -263,27 +262,8 @@ size_t ConfigBasedDataPipeline::super_resolve_yuv_workspace_bytes(unsigned w, un
 void ConfigBasedDataPipeline::super_resolve_yuv(const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst, unsigned w,
                                                 unsigned h, unsigned cx, unsigned cy, unsigned scale,
                                                 bool full_range, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
-  check_initialized(LOAD_KERNEL_LAYERS);
-  GpuAllocationPool own;  // the pipeline's flat parameters
-  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_yuv needs the pipeline's flat parameters");
-  srcnn_net nt = net();
-  const int range = full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED;
-  if (stream) {
-    check(srcnn_upscale_yuv(&nt, &src, &dst, w, h, cx, cy, scale, range, _context->fptr(_flat_params), ws, ws_bytes,
-                            stream),
-          "upscale_yuv");
-    return;
-  }
-  if (!_upscale_yuv_kernel) {
-    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
-                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
-                             " -D F3=" + std::to_string(nt.f3);
-    _upscale_yuv_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_yuv", 0, 0, 0, false, args);
-  }
-  srcnn::Context::Launch l(*_context, *_upscale_yuv_kernel);
-  check(srcnn_upscale_yuv(&nt, &src, &dst, w, h, cx, cy, scale, range, _context->fptr(_flat_params), ws, ws_bytes,
-                          _context->stream()),
-        "upscale_yuv");
+  const srcnn_yuv_format fmt{8, 0, SRCNN_YUV_PLANAR, cx, cy, full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED};
+  super_resolve_frame(fmt, src, dst, w, h, scale, ws, ws_bytes, stream);
 }
 
 void ConfigBasedDataPipeline::super_resolve_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src,
@@ -298,12 +278,9 @@ void ConfigBasedDataPipeline::super_resolve_frame(const srcnn_yuv_format& fmt, c
           "upscale_frame");
     return;
   }
-  if (!_upscale_frame_kernel) {
-    const std::string args = "-D N1=" + std::to_string(nt.n1) + " -D N2=" + std::to_string(nt.n2) +
-                             " -D F1=" + std::to_string(nt.f1) + " -D F2=" + std::to_string(nt.f2) +
-                             " -D F3=" + std::to_string(nt.f3);
-    _upscale_frame_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame", 0, 0, 0, false, args);
-  }
+  if (!_upscale_frame_kernel)
+    _upscale_frame_kernel =
+        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame", 0, 0, 0, false, net_defines());
   srcnn::Context::Launch l(*_context, *_upscale_frame_kernel);
   check(srcnn_upscale_frame(&nt, &fmt, &src, &dst, w, h, scale, _context->fptr(_flat_params), ws, ws_bytes,
                             _context->stream()),

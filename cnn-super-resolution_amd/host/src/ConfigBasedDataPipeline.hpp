@@ -112,22 +112,21 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * and reads the RGB result back.  Every output pixel passes through the
    * net: no border frame is left, also with scale 1. */
   void super_resolve(ImageData& low_res, unsigned scale, ImageData& result);
-  /** One planar Y'CbCr frame that is already on the device in, the frame of
-   * `scale` (1..4) times the size out: one srcnn_upscale_yuv call on the
-   * pipeline's flat parameters.  Only enqueues: no upload, no
-   * download, no allocation, no synchronisation, so a caller can keep several
-   * frames in flight, each with its own `stream`, workspace (`ws`, at least
-   * super_resolve_yuv_workspace_bytes) and device frames.  `stream` nullptr:
-   * the context's stream, and the call is counted (and in profile mode timed)
-   * as kernel 'srcnn_upscale_yuv'. */
+  /** super_resolve_frame for a planar frame of 8 bits per sample
+   * (DESIGN.md 14). */
   void super_resolve_yuv(const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst, unsigned w, unsigned h,
                          unsigned cx, unsigned cy, unsigned scale, bool full_range, void* ws, size_t ws_bytes,
                          srcnn_stream_t stream = nullptr);
-  /** super_resolve_yuv for every frame format of DESIGN.md 15 (8 to 16 bits
-   * per sample, planar or semi-planar chroma; `fmt` also holds the subsampling
-   * and the range): one srcnn_upscale_frame call, enqueued, counted and timed
-   * in the same way, as kernel 'srcnn_upscale_frame'; the workspace is
-   * super_resolve_yuv_workspace_bytes. */
+  /** One Y'CbCr frame that is already on the device in, the frame of `scale`
+   * (1..4) times the size out, in any frame format of DESIGN.md 15 (8 to 16
+   * bits per sample, planar or semi-planar chroma; `fmt` also holds the
+   * subsampling and the range): one srcnn_upscale_frame call on the pipeline's
+   * flat parameters.  Only enqueues: no upload, no download, no allocation, no
+   * synchronisation, so a caller can keep several frames in flight, each with
+   * its own `stream`, workspace (`ws`, at least
+   * super_resolve_yuv_workspace_bytes) and device frames.  `stream` nullptr:
+   * the context's stream, and the call is counted (and in profile mode timed)
+   * as kernel 'srcnn_upscale_frame'. */
   void super_resolve_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst,
                            unsigned w, unsigned h, unsigned scale, void* ws, size_t ws_bytes,
                            srcnn_stream_t stream = nullptr);
@@ -199,6 +198,8 @@ class ConfigBasedDataPipeline : public DataPipeline {
   void load_kernels(int load_flags) override;
 
  private:
+  /** the net shape as the defines a net-level kernel is created with */
+  std::string net_defines() const;
   void allocate_buffers(size_t w, size_t h);
   /** make the pools views of the flat buffers if they are unallocated;
    * true when the pools are the pipeline's flat views */
@@ -244,7 +245,6 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _train_kernel = nullptr;
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
-  Kernel* _upscale_yuv_kernel = nullptr;
   Kernel* _upscale_frame_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
   Kernel* _planes_kernel = nullptr;

@@ -200,89 +200,25 @@ Event DataPipeline::upscale_compose(ImageData& img, MemoryHandle org_img, Memory
 }
 
 Event DataPipeline::yuv_upscale_luma(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& luma_padded,
-                                     size_t scale, size_t padding, bool full_range, Event* ev) {
-  check_initialized(LOAD_KERNEL_LUMA);
-  require(scale >= 1 && scale <= 4, "yuv_upscale_luma: scale must be 1, 2, 3 or 4");
-  require(w > 0 && h > 0 && pitch_y >= w, "yuv_upscale_luma: empty plane or pitch below the width");
-  _context->wait(ev);
-  if (_context->raw_memory(y)->size < pitch_y * (h - 1) + w)
-    throw std::runtime_error("Invalid size of the Y plane buffer");
-  const size_t plane = (w * scale + padding) * (h * scale + padding) * sizeof(float);
-  if (!SRCNN_HAS_SIZE(luma_padded, plane)) luma_padded = _context->allocate(srcnn::MEM_READ_WRITE, plane);
-  if (!_yuv_upscale_luma_kernel)
-    _yuv_upscale_luma_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "yuv_upscale_luma");
-  srcnn::Context::Launch l(*_context, *_yuv_upscale_luma_kernel);
-  check(srcnn_yuv_upscale_luma(static_cast<const uint8_t*>(_context->ptr(y)), uint32_t(pitch_y),
-                               _context->fptr(luma_padded), uint32_t(w), uint32_t(h), uint32_t(scale),
-                               uint32_t(padding), full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED,
-                               _context->stream()),
-        "yuv_upscale_luma");
-  return _context->mark();
-}
-
-Event DataPipeline::upscale_planes_u8(MemoryHandle src0, MemoryHandle src1, size_t src_pitch, size_t pw, size_t ph,
-                                      MemoryHandle dst0, MemoryHandle dst1, size_t dst_pitch, size_t ow, size_t oh,
-                                      size_t scale, Event* ev) {
-  check_initialized(LOAD_KERNEL_LUMA);
-  require(scale >= 1 && scale <= 4, "upscale_planes_u8: scale must be 1, 2, 3 or 4");
-  require(pw > 0 && ph > 0 && ow > 0 && oh > 0 && src_pitch >= pw && dst_pitch >= ow,
-          "upscale_planes_u8: empty plane or pitch below the width");
-  _context->wait(ev);
-  for (MemoryHandle s : {src0, src1})
-    if (_context->raw_memory(s)->size < src_pitch * (ph - 1) + pw)
-      throw std::runtime_error("Invalid size of a source plane buffer");
-  for (MemoryHandle d : {dst0, dst1})
-    if (_context->raw_memory(d)->size < dst_pitch * (oh - 1) + ow)
-      throw std::runtime_error("Invalid size of a target plane buffer");
-  if (!_upscale_planes_u8_kernel)
-    _upscale_planes_u8_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "upscale_planes_u8");
-  srcnn::Context::Launch l(*_context, *_upscale_planes_u8_kernel);
-  check(srcnn_upscale_planes_u8(static_cast<const uint8_t*>(_context->ptr(src0)),
-                                static_cast<const uint8_t*>(_context->ptr(src1)), uint32_t(src_pitch), uint32_t(pw),
-                                uint32_t(ph), static_cast<uint8_t*>(_context->ptr(dst0)),
-                                static_cast<uint8_t*>(_context->ptr(dst1)), uint32_t(dst_pitch), uint32_t(ow),
-                                uint32_t(oh), uint32_t(scale), _context->stream()),
-        "upscale_planes_u8");
-  return _context->mark();
-}
-
-Event DataPipeline::yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y,
-                                     bool full_range, Event* ev) {
-  check_initialized(LOAD_KERNEL_LUMA);
-  require(w > 0 && h > 0 && pitch_y >= w, "yuv_compose_luma: empty plane or pitch below the width");
-  _context->wait(ev);
-  if (!SRCNN_HAS_SIZE(luma, w * h * sizeof(float))) throw std::runtime_error("Invalid size of new luma buffer");
-  if (_context->raw_memory(y)->size < pitch_y * (h - 1) + w)
-    throw std::runtime_error("Invalid size of the Y plane buffer");
-  if (!_yuv_compose_luma_kernel)
-    _yuv_compose_luma_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "yuv_compose_luma");
-  srcnn::Context::Launch l(*_context, *_yuv_compose_luma_kernel);
-  check(srcnn_yuv_compose_luma(_context->fptr(luma), static_cast<uint8_t*>(_context->ptr(y)), uint32_t(pitch_y),
-                               uint32_t(w), uint32_t(h), full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED,
-                               _context->stream()),
-        "yuv_compose_luma");
-  return _context->mark();
-}
-
-Event DataPipeline::yuv_upscale_luma16(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& luma_padded,
-                                       size_t scale, size_t padding, unsigned bits, bool msb, bool full_range,
-                                       Event* ev) {
+                                     size_t scale, size_t padding, unsigned bits, bool msb, bool full_range,
+                                     Event* ev) {
   check_initialized(LOAD_KERNEL_LUMA);
   const size_t B = bits > 8 ? 2 : 1;
-  require(scale >= 1 && scale <= 4, "yuv_upscale_luma16: scale must be 1, 2, 3 or 4");
-  require(w > 0 && h > 0 && pitch_y >= w * B, "yuv_upscale_luma16: empty plane or pitch below the row's bytes");
+  require(scale >= 1 && scale <= 4, "yuv_upscale_luma: scale must be 1, 2, 3 or 4");
+  require(w > 0 && h > 0 && pitch_y >= w * B, "yuv_upscale_luma: empty plane or pitch below the row's bytes");
   _context->wait(ev);
   if (_context->raw_memory(y)->size < pitch_y * (h - 1) + w * B)
     throw std::runtime_error("Invalid size of the Y plane buffer");
   const size_t plane = (w * scale + padding) * (h * scale + padding) * sizeof(float);
   if (!SRCNN_HAS_SIZE(luma_padded, plane)) luma_padded = _context->allocate(srcnn::MEM_READ_WRITE, plane);
-  if (!_yuv_upscale_luma16_kernel)
-    _yuv_upscale_luma16_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "yuv_upscale_luma16");
-  srcnn::Context::Launch l(*_context, *_yuv_upscale_luma16_kernel);
+  if (!_yuv_upscale_luma_kernel)
+    _yuv_upscale_luma_kernel =
+        _context->create_kernel(srcnn::KernelKind::Luma, bits == 8 ? "yuv_upscale_luma" : "yuv_upscale_luma16");
+  srcnn::Context::Launch l(*_context, *_yuv_upscale_luma_kernel);
   check(srcnn_yuv_upscale_luma16(_context->ptr(y), uint32_t(pitch_y), _context->fptr(luma_padded), uint32_t(w),
                                  uint32_t(h), uint32_t(scale), uint32_t(padding), bits, msb ? 1 : 0,
                                  full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED, _context->stream()),
-        "yuv_upscale_luma16");
+        "yuv_upscale_luma");
   return _context->mark();
 }
 
@@ -304,7 +240,8 @@ Event DataPipeline::upscale_planes(MemoryHandle src0, MemoryHandle src1, size_t 
     if (d && _context->raw_memory(d)->size < dst_pitch * (oh - 1) + ow * px)
       throw std::runtime_error("Invalid size of a target plane buffer");
   if (!_upscale_planes_kernel)
-    _upscale_planes_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "upscale_planes");
+    _upscale_planes_kernel = _context->create_kernel(
+        srcnn::KernelKind::SwapLuma, bits == 8 && !semiplanar ? "upscale_planes_u8" : "upscale_planes");
   srcnn::Context::Launch l(*_context, *_upscale_planes_kernel);
   check(srcnn_upscale_planes(_context->ptr(src0), src1 ? _context->ptr(src1) : nullptr, uint32_t(src_pitch),
                              uint32_t(pw), uint32_t(ph), _context->ptr(dst0), dst1 ? _context->ptr(dst1) : nullptr,
@@ -314,22 +251,23 @@ Event DataPipeline::upscale_planes(MemoryHandle src0, MemoryHandle src1, size_t 
   return _context->mark();
 }
 
-Event DataPipeline::yuv_compose_luma16(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y,
-                                       unsigned bits, bool msb, bool full_range, Event* ev) {
+Event DataPipeline::yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y,
+                                     unsigned bits, bool msb, bool full_range, Event* ev) {
   check_initialized(LOAD_KERNEL_LUMA);
   const size_t B = bits > 8 ? 2 : 1;
-  require(w > 0 && h > 0 && pitch_y >= w * B, "yuv_compose_luma16: empty plane or pitch below the row's bytes");
+  require(w > 0 && h > 0 && pitch_y >= w * B, "yuv_compose_luma: empty plane or pitch below the row's bytes");
   _context->wait(ev);
   if (!SRCNN_HAS_SIZE(luma, w * h * sizeof(float))) throw std::runtime_error("Invalid size of new luma buffer");
   if (_context->raw_memory(y)->size < pitch_y * (h - 1) + w * B)
     throw std::runtime_error("Invalid size of the Y plane buffer");
-  if (!_yuv_compose_luma16_kernel)
-    _yuv_compose_luma16_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "yuv_compose_luma16");
-  srcnn::Context::Launch l(*_context, *_yuv_compose_luma16_kernel);
+  if (!_yuv_compose_luma_kernel)
+    _yuv_compose_luma_kernel =
+        _context->create_kernel(srcnn::KernelKind::SwapLuma, bits == 8 ? "yuv_compose_luma" : "yuv_compose_luma16");
+  srcnn::Context::Launch l(*_context, *_yuv_compose_luma_kernel);
   check(srcnn_yuv_compose_luma16(_context->fptr(luma), _context->ptr(y), uint32_t(pitch_y), uint32_t(w), uint32_t(h),
                                  bits, msb ? 1 : 0, full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED,
                                  _context->stream()),
-        "yuv_compose_luma16");
+        "yuv_compose_luma");
   return _context->mark();
 }
 

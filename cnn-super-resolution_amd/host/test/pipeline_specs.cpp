@@ -528,6 +528,99 @@ void inference_spec(DataPipeline* p) {
   expect(back.w == img.w && back.h == img.h && back.bpp == 3, "result image dims");
 }
 
+// DataPipeline's three Y'CbCr launchers against the C ABI calls they wrap, byte
+// for byte (the padded plane: float for float), on shapes that take every path
+// of yuv.hip's staging: luma 19 x 12 at a pitch of 3 samples more (the clamped
+// single samples and the aligned words), chroma 10 x 6 at x2 cropped to 19 x 12
+// (a last tile cut by the plane).  The gaps of the pitched outputs keep their
+// bytes.  8 bits: the ABI's 8-bit entry points, else its general ones.
+void yuv_launchers_spec(DataPipeline* p, unsigned bits, bool msb, bool semi) {
+  auto& c = *p->context();
+  const size_t w = 19, h = 12, cw = 10, ch = 6, s = 2, pad = 12, W = s * w, H = s * h, CW = 19, CH = 12;
+  const size_t B = bits > 8 ? 2 : 1, nch = semi ? 2 : 1;
+  const bool full = bits > 8;  // one run per range
+  const int range = full ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED;
+  const unsigned char GAP = 0x5A;
+  uint32_t lcg = 12345u + bits;
+  auto next = [&] { return (lcg = lcg * 1664525u + 1013904223u) >> 8; };
+  // a plane of n samples a row at a pitch of 3 samples more, filled with
+  // values of `bits` bits (fill) or with the sentinel
+  auto plane = [&](size_t n, size_t rows, bool fill, size_t* pitch) {
+    *pitch = (n + 3) * B;
+    std::vector<unsigned char> v(*pitch * rows, GAP);
+    if (fill)
+      for (size_t i = 0; i < v.size() / B; ++i) {
+        const uint32_t word = (next() & ((1u << bits) - 1u)) << (msb ? 16 - bits : 0);
+        v[i * B] = (unsigned char)word;
+        if (B == 2) v[i * B + 1] = (unsigned char)(word >> 8);
+      }
+    return v;
+  };
+  auto to_device = [&](const std::vector<unsigned char>& v) {
+    MemoryHandle m = c.allocate(srcnn::MEM_READ_WRITE, v.size());
+    c.write_buffer(m, v.data(), true);
+    return m;
+  };
+  auto bytes_of = [&](MemoryHandle m) {
+    std::vector<unsigned char> v(c.raw_memory(m)->size);
+    c.block();
+    c.read_buffer(m, 0, v.size(), v.data(), true);
+    return v;
+  };
+  auto u8 = [&](MemoryHandle m) { return static_cast<uint8_t*>(c.ptr(m)); };
+  // the launchers' outputs (0) and the ABI's (1) are equal, and outside the
+  // n x B bytes of every row both still hold the sentinel
+  auto expect_same = [&](MemoryHandle a, MemoryHandle b, size_t n, size_t pitch, const char* what) {
+    const auto x = bytes_of(a), y = bytes_of(b);
+    expect(x == y, std::string(what) + ": the launcher and the C ABI differ");
+    for (size_t i = 0; i < x.size(); ++i)
+      expect(i % pitch < n * B || x[i] == GAP, std::string(what) + ": a byte between the rows was written");
+  };
+
+  size_t py, pc, PY, PC;
+  MemoryHandle y = to_device(plane(w, h, true, &py));
+  MemoryHandle c0 = to_device(plane(cw * nch, ch, true, &pc));
+  MemoryHandle c1 = semi ? MemoryHandle(0) : to_device(plane(cw * nch, ch, true, &pc));
+  MemoryHandle Y[2], C0[2], C1[2] = {0, 0}, padded[2] = {gpu_nullptr, gpu_nullptr};
+  for (int k = 0; k < 2; ++k) {
+    Y[k] = to_device(plane(W, H, false, &PY));
+    C0[k] = to_device(plane(CW * nch, CH, false, &PC));
+    if (!semi) C1[k] = to_device(plane(CW * nch, CH, false, &PC));
+  }
+  padded[1] = c.allocate(srcnn::MEM_READ_WRITE, (W + pad) * (H + pad) * sizeof(float));
+  std::vector<float> nl(W * H);  // the net's luma, past both ends of [0, 1]
+  for (auto& v : nl) v = float(next() % 1201) / 1000.f - 0.1f;
+  MemoryHandle luma = upload(c, nl);
+
+  p->yuv_upscale_luma(y, py, w, h, padded[0], s, pad, bits, msb, full);
+  p->upscale_planes(c0, c1, pc, cw, ch, C0[0], C1[0], PC, CW, CH, s, bits, msb, semi);
+  p->yuv_compose_luma(luma, W, H, Y[0], PY, bits, msb, full);
+  srcnn_stream_t st = c.stream();
+  if (bits == 8 && !semi) {
+    srcnn::check(srcnn_yuv_upscale_luma(u8(y), uint32_t(py), c.fptr(padded[1]), w, h, s, pad, range, st), "luma");
+    srcnn::check(srcnn_upscale_planes_u8(u8(c0), u8(c1), uint32_t(pc), cw, ch, u8(C0[1]), u8(C1[1]), uint32_t(PC), CW,
+                                         CH, s, st),
+                 "planes");
+    srcnn::check(srcnn_yuv_compose_luma(c.fptr(luma), u8(Y[1]), uint32_t(PY), W, H, range, st), "compose");
+  } else {
+    srcnn::check(srcnn_yuv_upscale_luma16(u8(y), uint32_t(py), c.fptr(padded[1]), w, h, s, pad, bits, msb, range, st),
+                 "luma");
+    srcnn::check(srcnn_upscale_planes(u8(c0), semi ? nullptr : u8(c1), uint32_t(pc), cw, ch, u8(C0[1]),
+                                      semi ? nullptr : u8(C1[1]), uint32_t(PC), CW, CH, s, bits, msb,
+                                      semi ? SRCNN_YUV_SEMIPLANAR : SRCNN_YUV_PLANAR, st),
+                 "planes");
+    srcnn::check(srcnn_yuv_compose_luma16(c.fptr(luma), u8(Y[1]), uint32_t(PY), W, H, bits, msb, range, st),
+                 "compose");
+  }
+
+  const auto f0 = download(c, padded[0], (W + pad) * (H + pad)), f1 = download(c, padded[1], (W + pad) * (H + pad));
+  expect(!std::memcmp(f0.data(), f1.data(), f0.size() * sizeof(float)),
+         "padded luma plane: the launcher and the C ABI differ");
+  expect_same(Y[0], Y[1], W, PY, "composed Y plane");
+  expect_same(C0[0], C0[1], CW * nch, PC, semi ? "UV plane" : "U plane");
+  if (!semi) expect_same(C1[0], C1[1], CW * nch, PC, "V plane");
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -568,6 +661,10 @@ int main(int argc, char** argv) {
   specs.push_back({"ConfigBasedDataPipeline - wide net (f2=5)", true,
                    [](DataPipeline* p) { cbdp_spec(p, 128, 64, 9, 5, 5, 25, 5, 3); }});
   specs.push_back({"ConfigBasedDataPipeline - forward + result image", true, inference_spec});
+  specs.push_back({"YuvLaunchers - 8 bits, planar", true,
+                   [](DataPipeline* p) { yuv_launchers_spec(p, 8, false, false); }});
+  specs.push_back({"YuvLaunchers - 10 bits, msb, semi-planar", true,
+                   [](DataPipeline* p) { yuv_launchers_spec(p, 10, true, true); }});
 
   srcnn::Context context;
   DataPipeline* pipeline = nullptr;

@@ -20,7 +20,7 @@
 //           or 9 to 16 bits as C420p10 and its kin; 4:2:0, 4:2:2 or 4:4:4,
 //           progressive) and is streamed: every frame is upscaled by S on the
 //           device as planar Y'CbCr -- luma through the net, chroma plain
-//           bicubic (srcnn_upscale_yuv; srcnn_upscale_frame above 8 bits) --
+//           bicubic (srcnn_upscale_frame) --
 //           and OUT is a Y4M of S times the size and the same depth with the
 //           same F, I, A, C and XCOLORRANGE tokens.  Two frame slots, each with its own stream, pinned host
 //           buffers, device frames and workspace: while one slot computes, the
@@ -428,9 +428,8 @@ struct FrameSlot {
   }
 };
 
-/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_yuv, or,
- * with more than 8 bits per sample, through srcnn_upscale_frame.  Any failed
- * call throws, which ends the run before another frame is started. */
+/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_frame.  Any
+ * failed call throws, which ends the run before another frame is started. */
 int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   namespace y4m = srcnn::y4m;
   y4m::Header hd = y4m::read_header(in);
@@ -480,11 +479,7 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
       break;
     }
     srcnn::check(srcnn_memcpy_h2d(s.dev_in, s.host_in, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
-    if (hd.bits > 8)
-      p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
-    else
-      p.super_resolve_yuv(s.src, s.dst, hd.w, hd.h, hd.cx, hd.cy, a.scale, hd.full_range, s.ws, ws_bytes,
-                          own_streams ? s.stream : nullptr);
+    p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
     s.busy = true;
   }
   for (unsigned i = 0; i < a.slots; ++i) drain(slots[(k + i) % a.slots]);  // the oldest first
@@ -500,7 +495,7 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
 }
 
 /** `cnn upscale`: the low-resolution image through srcnn_upscale, or a Y4M
- * video through srcnn_upscale_yuv frame by frame */
+ * video through srcnn_upscale_frame frame by frame */
 int upscale(ConfigBasedDataPipeline& p, const Args& a) {
   {
     std::ifstream in(a.in, std::ios::binary);

@@ -743,3 +743,54 @@ def test_preload_then_first_deep_frame(S):
     near = D.near_boundary(raw, 2e-3 * 4)
     assert np.array_equal(got[~near], D.encode(q, 10, 1)[~near])
     assert np.abs(D.decode(got, 10, 1) - q.astype(np.int64)).max() <= 1
+
+
+# ---- 10: the 8-bit and the general entry points keep their own names ----
+def test_each_entry_point_reports_under_its_own_name(S):
+    """The 8-bit entry points are the general ones at 8 bits, yet each of the
+    eight reports a rejected call under the name the caller used: scale 5 on a
+    5 x 3 frame gives SRCNN_ERR_INVALID and a message that starts with that
+    name and a colon; a workspace one byte short gives SRCNN_ERR_WORKSPACE from
+    the two net-level calls in the same way.  Nothing is launched: every buffer
+    keeps its bytes."""
+    net = S.Net(*NET)
+    w, h, cw, ch = 5, 3, 3, 2
+    params = torch.from_numpy(make_params(np.random.default_rng(1), NET, sd=0.05)).cuda()
+    nbytes = S.upscale_yuv_workspace_bytes(net, w, h, 2)
+    assert nbytes > 0
+    # room for a x5 frame of two-byte samples in every plane
+    y, u, v, Y, U, V = bufs = [torch.full((2 * 25 * w * h,), GAP, dtype=torch.uint8, device="cuda") for _ in range(6)]
+    ws = torch.full((max(nbytes, 4 * 25 * w * h),), GAP, dtype=torch.uint8, device="cuda")
+    f8 = S.yuv_format(8, 0, S.YUV_PLANAR, 2, 2, S.YUV_FULL)
+
+    def calls(s, ws_bytes):
+        W, Hh, CW, CH = s * w, s * h, (s * w - 1) // 2 + 1, (s * h - 1) // 2 + 1
+        src, dst = S.yuv_frame(y, u, v, w, cw), S.yuv_frame(Y, U, V, W, CW)
+        op = {
+            "yuv_upscale_luma": lambda: S.yuv_upscale_luma(y, w, ws, w, h, s, 0, S.YUV_FULL),
+            "yuv_upscale_luma16": lambda: S.yuv_upscale_luma16(y, 2 * w, ws, w, h, s, 0, 10, 0, S.YUV_FULL),
+            # (the two that take no scale: a pitch below the row)
+            "yuv_compose_luma": lambda: S.yuv_compose_luma(ws, Y, W - 1, W, Hh, S.YUV_FULL),
+            "yuv_compose_luma16": lambda: S.yuv_compose_luma16(ws, Y, 2 * W - 2, W, Hh, 10, 0, S.YUV_FULL),
+            "upscale_planes_u8": lambda: S.upscale_planes_u8(u, v, cw, cw, ch, U, V, CW, CW, CH, s),
+            "upscale_planes": lambda: S.upscale_planes(u, v, 2 * cw, cw, ch, U, V, 2 * CW, CW, CH, s, 10, 0,
+                                                       S.YUV_PLANAR),
+        }
+        net_level = {
+            "upscale_yuv": lambda: S.upscale_yuv(net, src, dst, w, h, 2, 2, s, S.YUV_FULL, params, ws, ws_bytes),
+            "upscale_frame": lambda: S.upscale_frame(net, f8, src, dst, w, h, s, params, ws, ws_bytes),
+        }
+        return op, net_level
+
+    def rejected(named, code):
+        for name, call in named.items():
+            with pytest.raises(S.SrcnnError) as e:
+                call()
+            assert e.value.code == code, name
+            assert S.last_error().startswith(name + ":"), (name, S.last_error())
+
+    op, net_level = calls(5, nbytes)
+    rejected(dict(op, **net_level), S.ERR_INVALID)
+    rejected(calls(2, nbytes - 1)[1], S.ERR_WORKSPACE)
+    for t in bufs + [ws]:
+        assert (H(t) == GAP).all(), "a rejected call wrote to a buffer"
