@@ -983,7 +983,7 @@ static bool plan_step(uint32_t w, uint32_t h, uint32_t batch, int arith, StepPla
   const int gd6 = grid_for_batch(batch, 256);  // d1x6
   const int gdf = p.kD1c ? (int)std::min<size_t>((size_t)batch * p.d1c_parts, kD1cGrid) : grid_for_batch(batch, 512);
   p.gd = p.x6 ? gd6 : gdf;
-  p.lds12 = p.x6 ? X6Lds(w, h).bytes : 0;
+  p.lds12 = p.x6 ? H6Lds(w, h).bytes : 0;
   const D6Lds ld6(w, h, p.rg, p.d3mode);
   p.ldsd = p.x6 ? ld6.bytes : p.kD1c ? d1c_lds_bytes(w, h) : 0;
   // d1x6 in delta3 mode: its form with the delta2 part images (d6tr.hpp) where

@@ -664,7 +664,14 @@ SRCNN_API int srcnn_get_path(void);
  * 1 = fp32 MFMA only (v_mfma_f32_32x32x2_f32 / 16x16x4_f32).
  * SRCNN_ARITH=f32 in the environment starts the library at 1.  For finite
  * operands below the bf16 maximum (|x| < 3.39e38) the results of the two
- * differ by fp32 rounding only.  Non-finite operands differ: arith 0 splits
+ * differ by fp32 rounding only.  The training step's two-part fp16 products
+ * (l12x6's layers 1 and 2, d1x6's gW1) scale each operand by a power of two
+ * taken from its largest magnitude -- W1 and W2 per launch, X and the bound on
+ * |A1| per sample -- so that rounding is relative to the operand's largest
+ * value in that sample or tensor (normwise, as an fp32 accumulation's is):
+ * an element more than about 2^17 below it carries fewer than 22 bits, and a
+ * sample whose bound max|X| max_c sum_tap |W1| + max|B1| passes fp32's range
+ * loses layer 2's precision.  Non-finite operands differ: arith 0 splits
  * +-inf (or a value that rounds to a bf16 infinity) into inf - inf = NaN
  * parts, so a product that arith 1 returns as +-inf comes out NaN, and the
  * split kernels' ReLU keeps a NaN that arith 1's fmaxf turns into 0

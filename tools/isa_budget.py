@@ -19,7 +19,8 @@ from collections import Counter, OrderedDict
 # 32 cycles when independent; 32x32x2 f32 every 64)
 MFMA_CYCLES = {"v_mfma_f32_16x16x4_f32": 32, "v_mfma_f32_16x16x4f32": 32,
                "v_mfma_f32_32x32x2_f32": 64, "v_mfma_f32_32x32x2f32": 64,
-               "v_mfma_f32_32x32x16_bf16": 32, "v_mfma_f32_16x16x32_bf16": 16}
+               "v_mfma_f32_32x32x16_bf16": 32, "v_mfma_f32_16x16x32_bf16": 16,
+               "v_mfma_f32_32x32x16_f16": 32}
 
 
 # per-wave ISSUE cost of one instruction (cycles), MI355X_MICROARCH.md
