@@ -1,5 +1,7 @@
-"""Helpers shared by the GPU tests: device buffers (torch, plumbing only),
-tolerance checks, synthetic SRCNN inputs."""
+"""Helpers shared by the tests, the tools and bench.py: device buffers (torch,
+plumbing only, imported where used), the net's parameter layout, tolerance
+checks, synthetic SRCNN inputs.  The fixtures and the training-step harness of
+the GPU tests are in tests/step_util.py."""
 import json
 import os
 
@@ -64,13 +66,61 @@ def log_record(rec):
             fh.write(json.dumps(rec) + "\n")
 
 
-def dev(a, torch):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def D(a, dtype=np.float32):
+    """A host array on the device."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
 
-def host(t, torch):
+def H(t):
+    """A device tensor as a host array of its own, after a synchronize."""
+    import torch
     torch.cuda.synchronize()
-    return t.detach().cpu().numpy()
+    return t.cpu().numpy().copy()
+
+
+# The flat parameter / gradient vector of a net cfg = (n1, n2, f1, f2, f3)
+NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
+
+
+def offsets(cfg):
+    """The seven boundaries of NAMES' segments (srcnn_net_offsets + [P];
+    tests/test_hip_util_cpu.py holds the two together)."""
+    n1, n2, f1, f2, f3 = cfg
+    return np.cumsum([0, f1 * f1 * n1, n1, f2 * f2 * n1 * n2, n2, f3 * f3 * n2, 1])
+
+
+def segments(cfg, flat):
+    """W1, B1, W2, B2, W3, B3 as views of a flat vector."""
+    off = offsets(cfg)
+    return [flat[off[i]:off[i + 1]] for i in range(6)]
+
+
+def dims(cfg, w, h):
+    """(w1, h1, w2, h2, w3, h3): the sizes of A1, A2 and A3 for a w x h tile."""
+    n1, n2, f1, f2, f3 = cfg
+    w1, h1 = w - f1 + 1, h - f1 + 1
+    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
+    return w1, h1, w2, h2, w2 - f3 + 1, h2 - f3 + 1
+
+
+def act_sizes(cfg, w, h, batch):
+    """The element counts of A1, A2 and A3."""
+    w1, h1, w2, h2, w3, h3 = dims(cfg, w, h)
+    return batch * w1 * h1 * cfg[0], batch * w2 * h2 * cfg[1], batch * w3 * h3
+
+
+def ran_x6(kernels):
+    """Whether a split-arithmetic kernel is among srcnn_last_kernels' names
+    (l12x6_fwd, d1x6_d3, wl1x6_fwd, wgrad2x6, ...; none runs under
+    srcnn_set_arith(1))."""
+    return any("x6" in k for k in kernels)
+
+
+def normwise(got, ref64):
+    got = np.asarray(got, np.float64)
+    ref64 = np.asarray(ref64, np.float64)
+    return float(np.linalg.norm(got - ref64) / max(np.linalg.norm(ref64), 1e-300))
 
 
 # Guard bands (tests/test_memory_hygiene_gpu.py): GUARD_FLOATS floats in front
@@ -218,6 +268,12 @@ def assert_close(got, ref, rtol=RTOL, what="", ref64=None, abs_floor=0.0, mag=No
                              "%.2e rel + %.1e x max (max rel err %.3e; fp32 oracle's own %.3e)"
                              % (what, n_over, n_sig, bound, abs_floor, el, el_ref))
     return err
+
+
+def check_gradients(cfg, got, rg, xg, tag):
+    """Each gradient segment of `got` against both oracles' (rg fp32, xg fp64)."""
+    for nm, g, r, x in zip(NAMES, segments(cfg, got), segments(cfg, rg), segments(cfg, xg)):
+        assert_close(g, r, RTOL, tag + "grad " + nm, x, FLIP_FLOOR)
 
 
 def smooth_patches(rng, batch, w, h, up=4):

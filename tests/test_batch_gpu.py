@@ -18,7 +18,8 @@ import pytest
 import batch_ref as B
 import hip_util
 from conftest import ROOT
-from hip_util import guarded, guards_intact, same_bits
+from hip_util import H, guarded, guards_intact, same_bits
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,27 +34,6 @@ SCALE = 2
 # footprint that is not swapped when it should be is another window.
 STAGE_FLOATS = 2048
 SHAPES = [(33, 33), (1, 1), (13, 9), (9, 13), (45, 44), (47, 46)]  # (tw, th)
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 def random_rgba(W, Hh, seed):

@@ -18,6 +18,7 @@ import pytest
 import srcnn_oracle as orc
 from conftest import ROOT
 from hip_util import RTOL, assert_close, max_rel_err
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -26,68 +26,23 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-import hip_util
-from hip_util import FLIP_FLOOR, RTOL, assert_close, guarded, guards_intact, make_batch, make_params, same_bits
+from hip_util import NAMES, check_gradients, dims, make_batch, make_params, normwise, same_bits, segments
+from step_util import S, _settings, no_x6, ran, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 CFG = (64, 32, 9, 1, 5)
-N1, N2, F1, F2, F3 = CFG
-OFF = np.cumsum([0, F1 * F1 * N1, N1, N1 * N2, N2, F3 * F3 * N2, 1])
-NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
 CASES = [("one", 33, 33, 5, "d1x6_d3", 31), ("many", 19, 17, 770, "d1x6_d3", 32), ("scratch", 27, 37, 3, "d1x6_d3_sc", 33),
          ("jumps", 33, 33, 520, "d1x6_d3", 34)]
 ZERO_SAMPLE = 515
 
 
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
-
-
-def normwise(a, ref):
-    return float(np.linalg.norm(np.asarray(a, np.float64) - ref) / np.linalg.norm(ref))
-
-
-def run_step(S, arith, w, h, batch, X, T, params, form=None, keep_ws=False):
-    net = S.Net(*CFG)
-    S.set_arith(arith)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = guarded(nbytes // 4, float("nan"))
-    g, err = guarded(np.zeros(params.size, np.float32), 1e30), guarded(1, 1e30, inner=0.0)
-    S.train_fwd_bwd(net, guarded(X, 1e30), guarded(T, 1e30), w, h, batch, guarded(params, 1e30), g, err, ws, nbytes)
-    ks = S.last_kernels()
-    if form is not None:
-        assert S.last_path() == "fused", S.last_path()
-        assert "l12x6_fwd" in ks and "l3r_d3" in ks, ks
-        assert [k for k in ks if k in ("d1x6_d3", "d1x6_d3_sc")] == [form], ks
-    else:
-        assert "x6" not in ks, ks
-    got = H(g)
-    if keep_ws:
-        return got, net, ws, nbytes
-    guards_intact(g, err, ws)
-    return got
+def grads(S, arith, w, h, batch, X, T, params, form=None):
+    """The step's gradients on guarded buffers; under split arithmetic (a
+    `form` given) l12x6_fwd, l3r_d3 and that form of d1x6 must have run, under
+    fp32 arithmetic no split kernel."""
+    expect = ran("fused", ["l12x6_fwd", "l3r_d3"], form) if form is not None else no_x6
+    return run_step(S, CFG, w, h, batch, X, T, params, arith=arith, guard=True, expect=expect).grads
 
 
 def inputs(S, name, w, h, batch, seed):
@@ -96,12 +51,9 @@ def inputs(S, name, w, h, batch, seed):
     params = make_params(rng, CFG, sd=0.05)
     if name == "jumps":
         # a first step for the net's own output of the zero sample
-        _, net, ws, nbytes = run_step(S, 0, w, h, batch, X, T, params, keep_ws=True)
-        sizes = (batch * (w - 8) * (h - 8) * N1, batch * (w - 8) * (h - 8) * N2, batch * (w - 12) * (h - 12))
-        outs = [guarded(n, 1e30) for n in sizes]
-        S.train_activations(net, w, h, batch, ws, nbytes, *outs)
-        a3 = H(outs[2]).reshape(batch, h - 12, w - 12)
-        hip_util._GUARDS.clear()
+        a3 = run_step(S, CFG, w, h, batch, X, T, params, guard=True, hold=True).activations()[2]
+        w3, h3 = dims(CFG, w, h)[4:]
+        a3 = a3.reshape(batch, h3, w3)
         t = T.reshape(batch, h, w).copy()
         t[256:512] *= np.float32(1024.0)
         t[ZERO_SAMPLE, 6:h - 6, 6:w - 6] = a3[ZERO_SAMPLE]
@@ -115,22 +67,19 @@ def test_gw1_two_part_f16(S, name, w, h, batch, form, seed):
     g0 = np.zeros(params.size, np.float32)
     rg, _ = orc.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
-    got = run_step(S, 0, w, h, batch, X, T, params, form)
-    f32 = run_step(S, 1, w, h, batch, X, T, params)
+    got = grads(S, 0, w, h, batch, X, T, params, form)
+    f32 = grads(S, 1, w, h, batch, X, T, params)
     dump = os.environ.get("SRCNN_GW1_DUMP")
     if dump:
         os.makedirs(dump, exist_ok=True)
         np.save(os.path.join(dump, name + ".npy"), got)
     errs = {}
-    for i, nm in enumerate(NAMES[:2]):
-        sl = slice(OFF[i], OFF[i + 1])
-        errs[nm] = (normwise(got[sl], xg[sl]), normwise(f32[sl], xg[sl]))
+    for nm, g, f, x in zip(NAMES[:2], segments(CFG, got), segments(CFG, f32), segments(CFG, xg)):
+        errs[nm] = (normwise(g, x), normwise(f, x))
         print("%s g%s: f16 x3 %.3e  fp32 arithmetic %.3e" % (name, nm, *errs[nm]))
     bar = 1.5 * max(e[1] for e in errs.values())
     for nm, (es, _) in errs.items():
         assert es <= bar, (name, nm, es, bar)
-    for i, nm in enumerate(NAMES):
-        sl = slice(OFF[i], OFF[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "gw1 f16 %s grad %s" % (name, nm), xg[sl], FLIP_FLOOR)
-    got2 = run_step(S, 0, w, h, batch, X, T, params, form)
+    check_gradients(CFG, got, rg, xg, "gw1 f16 %s " % name)
+    got2 = grads(S, 0, w, h, batch, X, T, params, form)
     assert same_bits(got, got2), "two runs differ"

@@ -50,19 +50,14 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-import hip_util
-from hip_util import FLIP_FLOOR, RTOL, assert_close, guarded, guards_intact, make_batch, make_params, same_bits
+from hip_util import check_gradients, dims, make_batch, make_params, offsets, same_bits
+from step_util import S, _settings, centre_params, ran, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 CFG = (64, 32, 9, 1, 5)
 N1, N2, F1, F2, F3 = CFG
-OFF = np.cumsum([0, F1 * F1 * N1, N1, N1 * N2, N2, F3 * F3 * N2, 1])
-NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
-KERNELS = ["l12x6_fwd", "l3r_d3"]
-D1X6_FORMS = ("d1x6_d3", "d1x6_d3_sc")
+OFF = offsets(CFG)
 SCRATCH_FORM = {(27, 37, 3)}  # shapes whose part images do not fit: the rest take them
 SHAPES = [(19, 17, 3), (17, 19, 3), (30, 30, 3), (33, 33, 258), (19, 17, 770), (27, 37, 3)]
 SPIKE_SHAPES = [(30, 30, 3), (19, 17, 3)]
@@ -70,40 +65,8 @@ CORNERS = ["top_left", "top_right", "bottom_left", "bottom_right"]
 SEEDS = {(19, 17, 3): 21, (17, 19, 3): 22, (30, 30, 3): 23, (33, 33, 258): 24, (19, 17, 770): 25,
          (27, 37, 3): 26}
 
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
-
-
 _BASE = {}
 _REF = {}
-
-
-def mid(a):
-    """Midway between the two middle values (at the median itself one value
-    would be 0 up to rounding and its ReLU decision a coin toss)."""
-    s = np.sort(np.asarray(a, np.float64), axis=0)
-    k = s.shape[0] // 2
-    return 0.5 * (s[k - 1] + s[k])
 
 
 def base_inputs(w, h, batch, all_positive=False):
@@ -115,21 +78,11 @@ def base_inputs(w, h, batch, all_positive=False):
         rng = np.random.default_rng(SEEDS[(w, h, batch)])
         X, T = make_batch(rng, batch, w, h)
         params = make_params(rng, CFG, sd=0.05)
-        A1 = orc.conv_fwd(X, params[OFF[0]:OFF[1]], params[OFF[1]:OFF[2]], w, h, 1, N1, F1, 1, batch)
-        Z = orc.conv_fwd(A1, params[OFF[2]:OFF[3]], np.zeros(N2, np.float32), w - 8, h - 8, N1, N2, F2, 0, batch)
-        params[OFF[3]:OFF[4]] = (-mid(np.asarray(Z).reshape(-1, N2))).astype(np.float32)
-        a3 = np.asarray(orc.forward(CFG, X, w, h, batch, params), np.float64).ravel()
-        params[-1] -= np.float32(a3.min() - 0.1 if all_positive else mid(a3))
+        centre_params(CFG, X, w, h, batch, params, all_positive=all_positive)
         for a in (X, T, params):
             a.setflags(write=False)
         _BASE[key] = (X, T, params)
     return _BASE[key]
-
-
-def check_gradients(got, rg, xg, tag):
-    for i, nm in enumerate(NAMES):
-        sl = slice(OFF[i], OFF[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, tag + "grad " + nm, xg[sl], FLIP_FLOOR)
 
 
 def oracles(w, h, batch, X, T, params, tag):
@@ -138,7 +91,7 @@ def oracles(w, h, batch, X, T, params, tag):
     g0 = np.zeros(params.size, np.float32)
     rg, _ = orc.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
-    check_gradients(rg, rg, xg, tag + "fp32 oracle alone: ")
+    check_gradients(CFG, rg, rg, xg, tag + "fp32 oracle alone: ")
     return rg, xg
 
 
@@ -147,8 +100,9 @@ def reference(w, h, batch):
     if key not in _REF:
         X, T, params = base_inputs(w, h, batch)
         rg, xg = oracles(w, h, batch, X, T, params, "%dx%d b%d " % key)
+        w1, h1 = dims(CFG, w, h)[:2]
         a1 = orc.conv_fwd(X, params[OFF[0]:OFF[1]], params[OFF[1]:OFF[2]], w, h, 1, N1, F1, 1, batch)
-        a2 = np.asarray(orc.conv_fwd(a1, params[OFF[2]:OFF[3]], params[OFF[3]:OFF[4]], w - 8, h - 8, N1, N2, F2, 1, batch))
+        a2 = np.asarray(orc.conv_fwd(a1, params[OFF[2]:OFF[3]], params[OFF[3]:OFF[4]], w1, h1, N1, N2, F2, 1, batch))
         share = (a2.reshape(-1, N2) > 0).mean(axis=0)
         assert share.min() >= 0.2 and share.max() <= 0.8, "%s: a channel's mask is not mixed: %s" % (key, share)
         for a in (rg, xg):
@@ -157,26 +111,12 @@ def reference(w, h, batch):
     return _REF[key]
 
 
-def run_step(S, w, h, batch, X, T, params, keep=False):
-    """One step on an exact-size NaN workspace: gradients (from zero) and what
-    srcnn_train_activations needs.  keep: the guarded views stay registered and
-    come back last, for the caller's guards_intact."""
-    net = S.Net(*CFG)
-    S.set_arith(0)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = guarded(nbytes // 4, float("nan"))
-    g, err = guarded(np.zeros(params.size, np.float32), 1e30), guarded(1, 1e30, inner=0.0)
-    S.train_fwd_bwd(net, guarded(X, 1e30), guarded(T, 1e30), w, h, batch, guarded(params, 1e30), g, err, ws, nbytes)
-    assert S.last_path() == "fused", S.last_path()
-    ks = S.last_kernels()
-    assert all(k in ks for k in KERNELS), ks
-    form = D1X6_FORMS[(w, h, batch) in SCRATCH_FORM]
-    assert [k for k in ks if k in D1X6_FORMS] == [form], ks
-    got = H(g)
-    if keep:
-        return net, got, ws, nbytes, (g, err, ws)
-    guards_intact(g, err, ws)
-    return net, got, ws, nbytes
+def step(S, w, h, batch, X, T, params, hold=False):
+    """One step on guarded buffers; l12x6_fwd, l3r_d3 and the shape's form of
+    d1x6 must have run."""
+    form = "d1x6_d3_sc" if (w, h, batch) in SCRATCH_FORM else "d1x6_d3"
+    return run_step(S, CFG, w, h, batch, X, T, params, guard=True, hold=hold,
+                    expect=ran("fused", ["l12x6_fwd", "l3r_d3"], form))
 
 
 @pytest.mark.parametrize("w,h,batch", SHAPES, ids=["%dx%d_b%d" % s for s in SHAPES])
@@ -184,15 +124,15 @@ def test_gradients(S, w, h, batch):
     """All six gradients against both oracles; two runs bit-identical."""
     rg, xg = reference(w, h, batch)
     X, T, params = base_inputs(w, h, batch)
-    _, got, _, _ = run_step(S, w, h, batch, X, T, params)
-    check_gradients(got, rg, xg, "gw2 operand %dx%d b%d " % (w, h, batch))
-    _, got2, _, _ = run_step(S, w, h, batch, X, T, params)
+    got = step(S, w, h, batch, X, T, params).grads
+    check_gradients(CFG, got, rg, xg, "gw2 operand %dx%d b%d " % (w, h, batch))
+    got2 = step(S, w, h, batch, X, T, params).grads
     assert same_bits(got, got2), "two runs differ"
 
 
 def spiked_target(T, a3, w, h, batch, corner):
     """T with the step's A3 in the output window, less 1 at the corner pixel."""
-    w3, h3, pad = w - 12, h - 12, 6
+    (w3, h3), pad = dims(CFG, w, h)[4:], 6
     t = np.array(T, np.float32).reshape(batch, h, w)
     t[:, pad:pad + h3, pad:pad + w3] = np.asarray(a3, np.float32).reshape(batch, h3, w3)
     y3 = 0 if corner.startswith("top") else h3 - 1
@@ -209,12 +149,7 @@ def own_a3(S, w, h, batch):
     key = (w, h, batch)
     if key not in _A3:
         X, T, params = base_inputs(w, h, batch, all_positive=True)
-        net, _, ws, nbytes, views = run_step(S, w, h, batch, X, T, params, keep=True)
-        sizes = (batch * (w - 8) * (h - 8) * N1, batch * (w - 8) * (h - 8) * N2, batch * (w - 12) * (h - 12))
-        outs = [guarded(n, 1e30) for n in sizes]
-        S.train_activations(net, w, h, batch, ws, nbytes, *outs)
-        a3 = H(outs[2])
-        guards_intact(*views, *outs)
+        a3 = step(S, w, h, batch, X, T, params, hold=True).activations()[2]
         assert a3.min() > 0.0, "A3 not positive everywhere: %g" % a3.min()
         a3.setflags(write=False)
         _A3[key] = a3
@@ -231,7 +166,7 @@ def test_gb2_single_pixel(S, w, h, batch, corner):
     tag = "gw2 operand %dx%d b%d %s " % (w, h, batch, corner)
     rg, xg = oracles(w, h, batch, X, T1, params, tag)
     assert np.abs(rg[OFF[3]:OFF[4]]).min() > 0.0, "oracle: a gB2 element without terms"
-    _, got, _, _ = run_step(S, w, h, batch, X, T1, params)
+    got = step(S, w, h, batch, X, T1, params).grads
     print(tag + "gB2 max |got - fp64| %g of max |gB2| %g"
           % (np.abs(got[OFF[3]:OFF[4]] - xg[OFF[3]:OFF[4]]).max(), np.abs(xg[OFF[3]:OFF[4]]).max()))
-    check_gradients(got, rg, xg, tag)
+    check_gradients(CFG, got, rg, xg, tag)

@@ -21,45 +21,19 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-import hip_util
-from hip_util import FLIP_FLOOR, RTOL, assert_close, guarded, guards_intact, make_batch, make_params, same_bits
+from hip_util import RTOL, assert_close, check_gradients, dims, make_batch, make_params, offsets, same_bits, segments
+from step_util import S, _settings, centre_params, ran, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 CFG = (64, 32, 9, 1, 5)
 N1, N2, F1, F2, F3 = CFG
-OFF = np.cumsum([0, F1 * F1 * N1, N1, N1 * N2, N2, F3 * F3 * N2, 1])
-NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
+OFF = offsets(CFG)
 KERNELS = ["l12x6_fwd", "l3r_d3", "d1x6_d3"]
 DEAD_SET = (1, 4, 7, 10, 13, 18, 21, 27, 30)
 # (w, h, batch) -> the seed of its inputs: chosen on the CPU so that the fp32
 # oracle's A2 is mixed for every case below
 SEEDS = {(17, 19, 3): 11, (33, 33, 600): 12, (30, 30, 3): 13}
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 _BASE = {}
@@ -84,42 +58,28 @@ def base_inputs(w, h, batch):
 def reference(w, h, batch, dead=(), centre=False):
     """Both oracles' gradients, activations and squared error for the shape's
     inputs with the channels `dead` of layer 2 switched off, computed once.
-    centre: every other channel's B2 is first moved to minus the median of its
-    pre-activation, as live_params does for layer 3.  As drawn (sd 0.05), B2
-    decides a channel's sign almost everywhere: about half of the channels are
-    dead and the rest always on, in the oracle too, so "a gradient on every
-    live channel" would not hold and no channel's mask would be mixed."""
+    centre: every other channel's B2 is first centred and layer 3's bias
+    after it (step_util.centre_params); otherwise "a gradient on every live
+    channel" would not hold and no channel's mask would be mixed."""
     key = (w, h, batch, tuple(dead), centre)
     if key not in _REF:
         X, T, params = base_inputs(w, h, batch)
         params = params.copy()
+        assert centre or not dead
         if centre:
-            A1 = orc.conv_fwd(X, params[OFF[0]:OFF[1]], params[OFF[1]:OFF[2]], w, h, 1, N1, F1, 1, batch)
-            Z = orc.conv_fwd(A1, params[OFF[2]:OFF[3]], np.zeros(N2, np.float32), w - 8, h - 8, N1, N2, F2, 0, batch)
-            # (midway between the two middle values: at the median itself one
-            # pre-activation per channel would be 0 up to rounding, and its
-            # ReLU decision a coin toss between any two fp32 summation orders)
-            zs = np.sort(np.asarray(Z, np.float64).reshape(-1, N2), axis=0)
-            k = zs.shape[0] // 2
-            params[OFF[3]:OFF[4]] = (-0.5 * (zs[k - 1] + zs[k])).astype(np.float32)
-        if dead:
-            params[OFF[3] + np.array(dead)] = -1e3
-        if dead or centre:
-            # layer 2 changed: half of A3 positive again (midway between the
-            # two middle outputs, for the same reason: delta3 is masked by A3 > 0)
-            a3 = np.sort(np.asarray(orc.forward(CFG, X, w, h, batch, params), np.float64).ravel())
-            params[-1] -= np.float32(0.5 * (a3[a3.size // 2 - 1] + a3[a3.size // 2]))
+            centre_params(CFG, X, w, h, batch, params, dead)
         g0 = np.zeros(params.size, np.float32)
         rg, _ = orc.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
         xg, _ = orc.f64.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
-        W1, B1, W2, B2, W3, B3 = (params[OFF[i]:OFF[i + 1]] for i in range(6))
+        W1, B1, W2, B2, W3, B3 = segments(CFG, params)
+        w1, h1, w2, h2, w3, h3 = dims(CFG, w, h)
         acts = []
         for m in (orc, orc.f64):
             A1 = m.conv_fwd(X, W1, B1, w, h, 1, N1, F1, 1, batch)
-            A2 = m.conv_fwd(A1, W2, B2, w - 8, h - 8, N1, N2, F2, 1, batch)
-            A3 = m.conv_fwd(A2, W3, B3, w - 8, h - 8, N2, 1, F3, 0, batch)
+            A2 = m.conv_fwd(A1, W2, B2, w1, h1, N1, N2, F2, 1, batch)
+            A3 = m.conv_fwd(A2, W3, B3, w2, h2, N2, 1, F3, 0, batch)
             acts.append({"A1": A1, "A2": A2, "A3": A3})
-        ref_err = orc.sq_err(T, acts[0]["A3"], w, h, w - 12, h - 12, batch)
+        ref_err = orc.sq_err(T, acts[0]["A3"], w, h, w3, h3, batch)
         # the masks are exercised: layer 2's (the bit mask) and layer 3's
         a2 = np.asarray(acts[0]["A2"]).reshape(-1, N2)
         pos2 = float((a2 > 0).mean())
@@ -134,26 +94,10 @@ def reference(w, h, batch, dead=(), centre=False):
     return _REF[key]
 
 
-def run_step(S, w, h, batch, params):
-    """One step on an exact-size NaN workspace: gradients (from zero), squared
-    error and the workspace (for srcnn_train_activations)."""
+def step(S, w, h, batch, params, hold=False):
+    """One step of the shape's inputs on guarded buffers; KERNELS must have run."""
     X, T, _ = base_inputs(w, h, batch)
-    net = S.Net(*CFG)
-    S.set_arith(0)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = guarded(nbytes // 4, float("nan"))
-    g, err = guarded(np.zeros(params.size, np.float32), 1e30), guarded(1, 1e30, inner=0.0)
-    S.train_fwd_bwd(net, guarded(X, 1e30), guarded(T, 1e30), w, h, batch, guarded(params, 1e30), g, err, ws, nbytes)
-    assert S.last_path() == "fused", S.last_path()
-    ks = S.last_kernels()
-    assert all(k in ks for k in KERNELS), ks
-    return net, H(g), float(H(err)[0]), g, err, ws, nbytes
-
-
-def check_gradients(got, rg, xg, tag):
-    for i, nm in enumerate(NAMES):
-        sl = slice(OFF[i], OFF[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, tag + "grad " + nm, xg[sl], FLIP_FLOOR)
+    return run_step(S, CFG, w, h, batch, X, T, params, guard=True, hold=hold, expect=ran("fused", KERNELS))
 
 
 @pytest.mark.parametrize("dead", [DEAD_SET] + [(n,) for n in range(N2)],
@@ -171,8 +115,8 @@ def test_dead_channels(S, dead):
             share = float((a2[:, n] > 0).mean())
             assert 0.2 <= share <= 0.8, "oracle: %.3f of live channel %d positive" % (share, n)
             assert rg[OFF[2]:OFF[3]].reshape(N1, N2)[:, n].any() and rg[OFF[3] + n] != 0.0
-    net, got, err, g, e, ws, nbytes = run_step(S, w, h, batch, params)
-    guards_intact(g, e, ws)
+    st = step(S, w, h, batch, params)
+    got, err = st.grads, st.sq_err
     gW2 = got[OFF[2]:OFF[3]].reshape(N1, N2)
     gB2 = got[OFF[3]:OFF[4]]
     print("dead %s: max |gW2[:, dead]| %g, max |gB2[dead]| %g, min live max|gW2[:, n]| %g, min live |gB2| %g"
@@ -184,7 +128,7 @@ def test_dead_channels(S, dead):
             assert not gW2[:, n].any() and gB2[n] == 0.0, "dead channel %d has a gradient" % n
         else:
             assert gW2[:, n].any() and gB2[n] != 0.0, "live channel %d has no gradient" % n
-    check_gradients(got, rg, xg, "d3 mask %dx%d dead %s " % (w, h, "set" if len(dead) > 1 else dead[0]))
+    check_gradients(CFG, got, rg, xg, "d3 mask %dx%d dead %s " % (w, h, "set" if len(dead) > 1 else dead[0]))
     assert err == pytest.approx(ref_err, rel=1e-4)
 
 
@@ -193,17 +137,13 @@ def test_samples_per_block(S, w, h, batch):
     """Gradients, squared error and A1 / A2 / A3 against both oracles; two runs
     bit-identical."""
     params, rg, xg, acts, ref_err = reference(w, h, batch)
-    net, got, err, g, e, ws, nbytes = run_step(S, w, h, batch, params)
+    st = step(S, w, h, batch, params, hold=True)
+    got, err = st.grads, st.sq_err
     tag = "d3 mask %dx%d b%d " % (w, h, batch)
-    check_gradients(got, rg, xg, tag)
+    check_gradients(CFG, got, rg, xg, tag)
     assert err == pytest.approx(ref_err, rel=1e-4)
-    sizes = (batch * (w - 8) * (h - 8) * N1, batch * (w - 8) * (h - 8) * N2, batch * (w - 12) * (h - 12))
-    outs = [guarded(n, 1e30) for n in sizes]
-    S.train_activations(net, w, h, batch, ws, nbytes, *outs)
-    a = dict(zip(("A1", "A2", "A3"), [H(o) for o in outs]))
-    guards_intact(g, e, ws, *outs)
+    a = dict(zip(("A1", "A2", "A3"), st.activations()))
     for nm in ("A1", "A2", "A3"):
         assert_close(a[nm], acts[0][nm], RTOL, tag + nm, acts[1][nm])
-    _, got2, err2, g2, e2, ws2, _ = run_step(S, w, h, batch, params)
-    guards_intact(g2, e2, ws2)
-    assert same_bits(got, got2) and err == err2, "two runs differ"
+    again = step(S, w, h, batch, params)
+    assert same_bits(got, again.grads) and err == again.sq_err, "two runs differ"

@@ -12,6 +12,7 @@ import os
 import pytest
 
 from conftest import GOLDEN, ROOT
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,14 +28,6 @@ def load_tool():
 
 
 tool = load_tool()
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
 
 
 @pytest.fixture(scope="module")
@@ -79,8 +72,8 @@ def test_wide_step_profiles_one_launch_per_kernel(S, arith):
     p, g = 0.05 * torch.randn(P, device="cuda"), torch.zeros(P, device="cuda")
     nbytes = S.train_workspace_bytes(net, size, size, batch)
     ws = torch.zeros(nbytes // 4 + 64, device="cuda")
+    S.set_arith(arith)
     try:
-        S.set_arith(arith)
         S.profile_reset()
         S.profile_enable(True)
         S.train_fwd_bwd(net, X, T, size, size, batch, p, g, None, ws, nbytes)
@@ -89,7 +82,6 @@ def test_wide_step_profiles_one_launch_per_kernel(S, arith):
         S.profile_enable(False)
         stats = S.profile_stats()
     finally:
-        S.set_arith(0)
         S.profile_enable(False)
         S.profile_reset()
     print(stats)

@@ -20,20 +20,13 @@ import pytest
 import srcnn_oracle as orc
 from conftest import ROOT
 from hip_util import FLIP_FLOOR, assert_close, make_batch, make_params
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 LR = [1e-4, 1e-4, 1e-5]
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
 
 
 def _free_port():

@@ -30,17 +30,14 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-import hip_util
-from hip_util import FLIP_FLOOR, RTOL, assert_close, guarded, guards_intact, make_batch, make_params, same_bits
+from hip_util import check_gradients, dims, make_batch, make_params, offsets, same_bits, segments
+from step_util import S, _settings, no_x6, ran, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 CFG = (64, 32, 9, 1, 5)
 N1, N2, F1, F2, F3 = CFG
-OFF = np.cumsum([0, F1 * F1 * N1, N1, N1 * N2, N2, F3 * F3 * N2, 1])
-NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
+OFF = offsets(CFG)
 LR = [1.0, 1e-4, 1e-5]  # the lazy case: layer 1's rate moves W1 by whole units
 ZERO, TINY = 1024, 1025
 CASES = [("one", 33, 33, 5, 41), ("many", 17, 19, 1030, 42), ("jumps", 17, 19, 1030, 42), ("padded", 21, 23, 3, 43),
@@ -62,67 +59,17 @@ def test_stride_branches_of_the_cases():
     assert not x6lds_padded(35, 35)
 
 
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
-
-
-def sizes(w, h, batch):
-    ow, oh = w - F1 + 1, h - F1 + 1
-    return batch * ow * oh * N1, batch * ow * oh * N2, batch * (ow - F3 + 1) * (oh - F3 + 1)
-
-
-def run_step(S, arith, w, h, batch, X, T, params, lazy=None, finite=True):
-    """-> (grads, A1, A2, A3, params the step ran on).  lazy: (pending grads,
-    momentum) of a pending update, applied by train_fwd_bwd_lazy."""
-    net = S.Net(*CFG)
-    S.set_arith(arith)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = guarded(nbytes // 4, float("nan"))
-    err = guarded(1, 1e30, inner=0.0)
-    Xd, Td = guarded(X, 1e30), guarded(T, 1e30)
-    if lazy is None:
-        g, p = guarded(np.zeros(params.size, np.float32), 1e30), guarded(params, 1e30)
-        S.train_fwd_bwd(net, Xd, Td, w, h, batch, p, g, err, ws, nbytes)
-        bufs, want, ran_on = [g, err, ws], "l12x6_fwd", params
-    else:
-        g, p_in, m_in = guarded(lazy[0], 1e30), guarded(params, 1e30), guarded(lazy[1], 1e30)
-        p_out, m_out = guarded(params.size, 1e30), guarded(params.size, 1e30)
-        S.train_fwd_bwd_lazy(net, Xd, Td, w, h, batch, p_in, p_out, m_in, m_out, g, 0.9, 1e-3, LR, batch, err, ws, nbytes)
-        bufs, want = [g, err, ws, p_out, m_out], "l12x6_fwd_lazy"
-    ks = S.last_kernels()
-    if arith == 0:
-        assert S.last_path() == "fused", S.last_path()
-        assert want in ks, ks
-    else:
-        assert "x6" not in ks, ks
-    grads = H(g)
-    ran_on = H(p_out) if lazy is not None else params
-    outs = [guarded(n, 1e30) for n in sizes(w, h, batch)]
-    S.train_activations(net, w, h, batch, ws, nbytes, *outs)
-    acts = [H(o) for o in outs]
-    guards_intact(*bufs, *outs)
+def step(S, arith, w, h, batch, X, T, params, lazy=None, finite=True):
+    """-> (grads, A1, A2, A3, params the step ran on) of a step on guarded
+    buffers.  lazy: (pending grads, momentum) of a pending update, applied by
+    train_fwd_bwd_lazy."""
+    expect = no_x6 if arith else ran("fused", ["l12x6_fwd" if lazy is None else "l12x6_fwd_lazy"])
+    st = run_step(S, CFG, w, h, batch, X, T, params, arith=arith, guard=True, hold=True, expect=expect,
+                  lazy=None if lazy is None else lazy + (LR,))
+    acts = st.activations()
     if finite:
         assert all(np.isfinite(a).all() for a in acts)
-    return grads, acts[0], acts[1], acts[2], ran_on
+    return st.grads, acts[0], acts[1], acts[2], st.params
 
 
 _INPUTS = {}
@@ -146,8 +93,8 @@ def inputs(name, w, h, batch, seed):
 
 
 def forward64(X, params, w, h, batch):
-    ow, oh = w - F1 + 1, h - F1 + 1
-    seg = [params[OFF[i]:OFF[i + 1]] for i in range(4)]
+    ow, oh = dims(CFG, w, h)[:2]
+    seg = segments(CFG, params)
     a1 = orc.f64.conv_fwd(X, seg[0], seg[1], w, h, 1, N1, F1, True, batch)
     a2 = orc.f64.conv_fwd(a1, seg[2], seg[3], ow, oh, N1, N2, F2, True, batch)
     return a1.reshape(batch, -1), a2.reshape(batch, -1)
@@ -174,26 +121,24 @@ def check_grads(name, got, X, T, params, w, h, batch):
     g0 = np.zeros(params.size, np.float32)
     rg, _ = orc.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(CFG, X, T, w, h, batch, params, g0)
-    for i, nm in enumerate(NAMES):
-        sl = slice(OFF[i], OFF[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "l12x6 f16 %s grad %s" % (name, nm), xg[sl], FLIP_FLOOR)
+    check_gradients(CFG, got, rg, xg, "l12x6 f16 %s " % name)
 
 
 @pytest.mark.parametrize("name,w,h,batch,seed", CASES, ids=[c[0] for c in CASES])
 def test_l12x6_two_part_f16(S, name, w, h, batch, seed):
     X, T, params = inputs(name, w, h, batch, seed)
-    got = run_step(S, 0, w, h, batch, X, T, params)
-    f32 = run_step(S, 1, w, h, batch, X, T, params)
+    got = step(S, 0, w, h, batch, X, T, params)
+    f32 = step(S, 1, w, h, batch, X, T, params)
     check_activations(name, got, f32, X, params, params, w, h, batch)
     if name == "jumps":
-        ow, oh = w - F1 + 1, h - F1 + 1
+        ow, oh = dims(CFG, w, h)[:2]
         a1 = got[1].reshape(batch, ow * oh, N1)[ZERO]
         b1 = np.maximum(params[OFF[1]:OFF[2]], np.float32(0))
         assert same_bits(a1, np.broadcast_to(b1, a1.shape)), "the zero sample's A1 is not relu(B1)"
         a2 = got[2].reshape(batch, ow * oh, N2)[ZERO]
         assert same_bits(a2, np.broadcast_to(a2[0], a2.shape)), "the zero sample's A2 differs between pixels"
     check_grads(name, got[0], X, T, params, w, h, batch)
-    again = run_step(S, 0, w, h, batch, X, T, params)
+    again = step(S, 0, w, h, batch, X, T, params)
     assert all(same_bits(a, b) for a, b in zip(got[:4], again[:4])), "two runs differ"
 
 
@@ -205,24 +150,24 @@ def test_l12x6_lazy_scale_of_the_updated_weights(S):
     # lr = 1 on layer 1: the update moves every W1 weight by about N(0, 1)
     pend[OFF[0]:OFF[1]] = (batch * rng.standard_normal(OFF[1])).astype(np.float32)
     mom = np.zeros(params.size, np.float32)
-    got = run_step(S, 0, w, h, batch, X, T, params, lazy=(pend, mom))
-    f32 = run_step(S, 1, w, h, batch, X, T, params, lazy=(pend, mom))
+    got = step(S, 0, w, h, batch, X, T, params, lazy=(pend, mom))
+    f32 = step(S, 1, w, h, batch, X, T, params, lazy=(pend, mom))
     w_old, w_new = np.abs(params[OFF[0]:OFF[1]]).max(), np.abs(got[4][OFF[0]:OFF[1]]).max()
     print("lazy: max |W1| %.3g -> %.3g" % (w_old, w_new))
     assert w_new >= 8 * w_old  # under the old scale (max to [2^14, 2^15)) these pass fp16's 65504
     check_activations("lazy", got, f32, X, got[4], f32[4], w, h, batch)
     check_grads("lazy", got[0], X, T, got[4], w, h, batch)
-    again = run_step(S, 0, w, h, batch, X, T, params, lazy=(pend, mom))
+    again = step(S, 0, w, h, batch, X, T, params, lazy=(pend, mom))
     assert all(same_bits(a, b) for a, b in zip(got, again)), "two runs differ"
 
 
 def test_l12x6_non_finite_pixel_stays_in_its_sample(S):
     name, w, h, batch, seed = CASES[1]
     X, T, params = inputs(name, w, h, batch, seed)
-    clean = run_step(S, 0, w, h, batch, X, T, params)
+    clean = step(S, 0, w, h, batch, X, T, params)
     x = X.reshape(batch, -1).copy()
     x[3, (h // 2) * w + w // 2] = np.inf
-    dirty = run_step(S, 0, w, h, batch, x.ravel(), T, params, finite=False)
+    dirty = step(S, 0, w, h, batch, x.ravel(), T, params, finite=False)
     keep = np.arange(batch) != 3
     for nm, a, b in (("A1", clean[1], dirty[1]), ("A2", clean[2], dirty[2])):
         a, b = a.reshape(batch, -1), b.reshape(batch, -1)

@@ -26,41 +26,16 @@ import pytest
 
 import srcnn_oracle as orc
 import hip_util
-from hip_util import (FLIP_FLOOR, RTOL, assert_close, guarded, guards_intact, make_batch, make_params,
-                      same_bits)
+from hip_util import (H, RTOL, act_sizes, assert_close, check_gradients, dims, guarded, guards_intact, make_batch,
+                      make_params, same_bits, segments)
+from step_util import S, _settings, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
 
 NETS = {"default": (64, 32, 9, 1, 5), "wide": (128, 64, 9, 5, 5), "tiny": (8, 4, 5, 1, 3),
         "example": (32, 16, 9, 1, 5), "default_f3": (64, 32, 9, 1, 3)}
 FILLS = (0.0,) + hip_util.POISONS  # zeros, NaN, +1e30
 LR = [1e-4, 2e-4, 1e-5]
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    """Every test leaves the library on the auto path and split arithmetic."""
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 def assert_runs_identical(runs, what):
@@ -76,14 +51,6 @@ def assert_runs_identical(runs, what):
                     "%s: %s differs between fill 0 and fill %r at %d of %d elements (first %s: %r vs %r)"
                     % (what, nm, fill, d.size, a.size, d[:6].tolist(), a.ravel()[d[:3]].tolist(),
                        b.ravel()[d[:3]].tolist()))
-
-
-def act_sizes(cfg, w, h, batch):
-    n1, n2, f1, f2, f3 = cfg
-    w1, h1 = w - f1 + 1, h - f1 + 1
-    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
-    w3, h3 = w2 - f3 + 1, h2 - f3 + 1
-    return batch * w1 * h1 * n1, batch * w2 * h2 * n2, batch * w3 * h3
 
 
 def check_kernels(S, path, kernels):
@@ -415,15 +382,15 @@ def d3_reference(w, h, batch):
         g0 = (1e-3 * rng.standard_normal(params.size)).astype(np.float32)
         rg, _ = orc.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
         xg, _ = orc.f64.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
-        o = np.cumsum([0, f1 * f1 * n1, n1, n1 * n2, n2, f3 * f3 * n2, 1])
-        W1, B1, W2, B2, W3, B3 = (params[o[i]:o[i + 1]] for i in range(6))
+        W1, B1, W2, B2, W3, B3 = segments(cfg, params)
+        w1, h1, w2, h2, w3, h3 = dims(cfg, w, h)
         acts = []
         for m in (orc, orc.f64):  # (fp32 oracle, fp64 oracle): A1, A2 after ReLU, A3 linear
             A1 = m.conv_fwd(X, W1, B1, w, h, 1, n1, f1, 1, batch)
-            A2 = m.conv_fwd(A1, W2, B2, w - 8, h - 8, n1, n2, f2, 1, batch)
-            A3 = m.conv_fwd(A2, W3, B3, w - 8, h - 8, n2, 1, f3, 0, batch)
+            A2 = m.conv_fwd(A1, W2, B2, w1, h1, n1, n2, f2, 1, batch)
+            A3 = m.conv_fwd(A2, W3, B3, w2, h2, n2, 1, f3, 0, batch)
             acts.append({"A1": A1, "A2": A2, "A3": A3})
-        ref_err = orc.sq_err(T, acts[0]["A3"], w, h, w - 12, h - 12, batch)
+        ref_err = orc.sq_err(T, acts[0]["A3"], w, h, w3, h3, batch)
         assert_live(acts[0]["A3"], rg, g0, "sweep reference %dx%d" % (w, h))
         ref = (X, T, params, g0, rg, xg, acts, ref_err)
         for a in ref[:6] + tuple(acts[0].values()) + tuple(acts[1].values()):
@@ -440,32 +407,21 @@ def test_d3_mode_run_geometry_sweep(S, w, h, d3, arith):
     under split arithmetic through l3r_d3 + d1x6_d3 (asserted), under fp32
     through d1c.  Exact-size NaN-poisoned workspace."""
     cfg = NETS["default"]
-    net = S.Net(*cfg)
     batch = 3
     X, T, params, g0, rg, xg, acts, ref_err = d3_reference(w, h, batch)
-    P = params.size
-    S.set_arith(arith)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = guarded(nbytes // 4, float("nan"))
-    g, err = guarded(g0, 1e30), guarded(1, 1e30, inner=0.0)
-    S.train_fwd_bwd(net, guarded(X, 1e30), guarded(T, 1e30), w, h, batch, guarded(params, 1e30), g, err, ws,
-                    nbytes)
-    assert S.last_path() == "fused", S.last_path()
-    ks = S.last_kernels()
     if arith == 0:
         want = ["l12x6_fwd", "l3r_d3", "d1x6_d3"] if d3 else ["l12x6_fwd", "l3_op_level", "d1x6_grad12"]
     else:
         want = ["l12_fwd", "l3r_delta" if d3 else "l3_op_level", "d1c_grad12"]
-    assert all(k in ks for k in want), (ks, want)
-    assert ("d1x6_d3" in ks) == (d3 and arith == 0), ks
+
+    def expect(path, ks):
+        assert path == "fused", path
+        assert all(k in ks for k in want), (ks, want)
+        assert ("d1x6_d3" in ks) == (d3 and arith == 0), ks
+    st = run_step(S, cfg, w, h, batch, X, T, params, g0, arith=arith, guard=True, hold=True, expect=expect)
     tag = "d3 sweep %dx%d %s " % (w, h, "f32" if arith else "split")
-    got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, tag + "grad " + nm, xg[sl], FLIP_FLOOR)
-    assert float(H(err)[0]) == pytest.approx(ref_err, rel=1e-4)
-    a = read_activations(S, net, cfg, w, h, batch, ws, nbytes, 1e30)
-    guards_intact(g, err, ws)
+    check_gradients(cfg, st.grads, rg, xg, tag)
+    assert st.sq_err == pytest.approx(ref_err, rel=1e-4)
+    a = dict(zip(("A1", "A2", "A3"), st.activations()))
     for nm in ("A1", "A2", "A3"):
         assert_close(a[nm], acts[0][nm], RTOL, tag + nm, acts[1][nm])

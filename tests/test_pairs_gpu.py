@@ -16,7 +16,8 @@ import pytest
 import hip_util
 import pairs_ref as P
 from conftest import ROOT
-from hip_util import guarded, guards_intact, same_bits
+from hip_util import H, guarded, guards_intact, same_bits
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,27 +32,6 @@ CNN = os.path.join(ROOT, "cnn-super-resolution_amd", "bin", "cnn")
 SHAPES = [(1, 1), (2, 3), (5, 4), (17, 9), (37, 23), (135, 37)]
 EXEMPT_BAND = 1e-3  # distance of the reference's unrounded value from a half-integer
 EXEMPT_CAP = 0.01
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 def random_rgba(W, Hh, seed):

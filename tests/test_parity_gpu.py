@@ -16,19 +16,13 @@ import pytest
 
 import srcnn_oracle as orc
 from conftest import GOLDEN
-from hip_util import FLIP_FLOOR, RTOL, assert_close, make_batch, make_params
+from hip_util import (D, H, RTOL, act_sizes, assert_close, check_gradients, dims, make_batch, make_params, ran_x6,
+                      segments)
+from step_util import S, _settings, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
 
 
 @pytest.fixture(params=[0, 1], ids=["auto", "generic"])
@@ -41,15 +35,6 @@ def path(request, S):
 def load(name):
     with open(os.path.join(GOLDEN, name)) as fh:
         return json.load(fh)
-
-
-def D(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 def zeros(n, dtype=torch.float32):
@@ -421,22 +406,14 @@ def test_train_step_vs_oracle(S, path, name, batch, size):
     g0 = (1e-3 * rng.standard_normal(P)).astype(np.float32)
     rg, acts = orc.train_fwd_bwd(cfg, X, T, size, size, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(cfg, X, T, size, size, batch, params, g0)
-    nbytes = S.train_workspace_bytes(net, size, size, batch)
-    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g = D(g0)
-    err = zeros(1)
-    S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), g, err, ws, nbytes)
-    assert S.last_path() in expected_train_path(name, size, path), S.last_path()
-    got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "grad " + nm, xg[sl], FLIP_FLOOR)
+    st = run_step(S, cfg, size, size, batch, X, T, params, g0)
+    assert st.path in expected_train_path(name, size, path), st.path
+    check_gradients(cfg, st.grads, rg, xg, "")
     # validation metric over the same forward
-    pad = cfg[2] + cfg[3] + cfg[4] - 3
+    w3, h3 = dims(cfg, size, size)[4:]
     A3 = orc.forward(cfg, X, size, size, batch, params)
-    ref_err = orc.sq_err(T, A3, size, size, size - pad, size - pad, batch)
-    assert float(H(err)[0]) == pytest.approx(ref_err, rel=1e-4)
+    ref_err = orc.sq_err(T, A3, size, size, w3, h3, batch)
+    assert st.sq_err == pytest.approx(ref_err, rel=1e-4)
     # update
     mom0 = (1e-3 * rng.standard_normal(P)).astype(np.float32)
     lr = [1e-4, 1e-4, 1e-5]
@@ -503,7 +480,6 @@ def test_train_step_nonsquare_tiles(S, w, h, batch):
     """Non-square training tiles through the fused kernels (l12, l3 / op-level
     layer 3, d1c: pixel -> X offsets and row clamps use ow != oh)."""
     cfg = NETS["default"]
-    net = S.Net(*cfg)
     rng = np.random.default_rng(7)
     X, T = make_batch(rng, batch, w, h)
     params = make_params(rng, cfg, sd=0.05)
@@ -511,16 +487,9 @@ def test_train_step_nonsquare_tiles(S, w, h, batch):
     g0 = np.zeros(P, np.float32)
     rg, _ = orc.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g = D(g0)
-    S.train_fwd_bwd(net, D(X), D(T), w, h, batch, D(params), g, None, ws, nbytes)
-    assert S.last_path() == "fused", S.last_path()
-    got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "grad " + nm, xg[sl], FLIP_FLOOR)
+    st = run_step(S, cfg, w, h, batch, X, T, params, sq_err=False)
+    assert st.path == "fused", st.path
+    check_gradients(cfg, st.grads, rg, xg, "")
 
 
 @pytest.mark.parametrize("size", [34, 37, 40])
@@ -532,7 +501,6 @@ def test_wide_tiles_past_the_wide_step(S, size, arith):
     (ConfigBasedDataPipeline.cpp:128-323: any tile size goes through
     execute_batch), gradients against the oracle."""
     cfg = NETS["wide"]
-    net = S.Net(*cfg)
     rng = np.random.default_rng(size)
     batch = 3
     X, T = make_batch(rng, batch, size, size)
@@ -541,28 +509,16 @@ def test_wide_tiles_past_the_wide_step(S, size, arith):
     g0 = (1e-3 * rng.standard_normal(P)).astype(np.float32)
     rg, _ = orc.train_fwd_bwd(cfg, X, T, size, size, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(cfg, X, T, size, size, batch, params, g0)
-    S.set_arith(arith)
-    try:
-        nbytes = S.train_workspace_bytes(net, size, size, batch)
-        ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-        g, err = D(g0), zeros(1)
-        S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), g, err, ws, nbytes)
-        path, kernels = S.last_path(), S.last_kernels()
-    finally:
-        S.set_arith(0)
+    st = run_step(S, cfg, size, size, batch, X, T, params, g0, arith=arith)
+    path, ks = st.path, st.kernels
     assert path == "fast", path
     assert path in expected_train_path("wide", size, 0)
-    ks = kernels
     assert ks == ["conv_fwd_l1:fast", "conv_fwd_l2:fast", "conv_fwd_l3:fast", "conv_delta_l2:fast",
                   "conv_delta_l1:fast", "conv_grad_l3:fast", "conv_grad_l2:fast", "conv_grad_l1:fast"], ks
-    got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "wide %d grad %s" % (size, nm), xg[sl], FLIP_FLOOR)
-    pad = cfg[2] + cfg[3] + cfg[4] - 3
+    check_gradients(cfg, st.grads, rg, xg, "wide %d " % size)
+    w3, h3 = dims(cfg, size, size)[4:]
     A3 = orc.forward(cfg, X, size, size, batch, params)
-    assert float(H(err)[0]) == pytest.approx(orc.sq_err(T, A3, size, size, size - pad, size - pad, batch), rel=1e-4)
+    assert st.sq_err == pytest.approx(orc.sq_err(T, A3, size, size, w3, h3, batch), rel=1e-4)
 
 
 def test_train_activations_follow_the_step_arith(S):
@@ -576,24 +532,19 @@ def test_train_activations_follow_the_step_arith(S):
     X, T = make_batch(rng, batch, size, size)
     params = make_params(rng, cfg, sd=0.05)
     P = params.size
-    n1, n2 = cfg[0], cfg[1]
-    A1ref = orc.conv_fwd(X, params[:81 * n1], params[81 * n1:82 * n1], size, size, 1, n1, 9, 1, batch)
-    w1 = size - cfg[2] + 1
-    w3 = w1 - cfg[4] + 1
+    W1, B1 = segments(cfg, params)[:2]
+    A1ref = orc.conv_fwd(X, W1, B1, size, size, 1, cfg[0], cfg[2], 1, batch)
     nbytes = S.train_workspace_bytes(net, size, size, batch)
     ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    try:
-        for arith_step, arith_read in ((0, 1), (1, 0)):
-            S.set_arith(arith_step)
-            S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), zeros(P), None, ws, nbytes)
-            step_kernels = S.last_kernels()
-            S.set_arith(arith_read)
-            A1d, A2d, A3d = zeros(batch * w1 * w1 * n1), zeros(batch * w1 * w1 * n2), zeros(batch * w3 * w3)
-            S.train_activations(net, size, size, batch, ws, nbytes, A1d, A2d, A3d)
-            assert any("x6" in k for k in step_kernels) == (arith_step == 0), step_kernels
-            assert_close(H(A1d), A1ref, RTOL, "A1 (step arith %d, read under %d)" % (arith_step, arith_read))
-    finally:
-        S.set_arith(0)
+    for arith_step, arith_read in ((0, 1), (1, 0)):
+        S.set_arith(arith_step)
+        S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), zeros(P), None, ws, nbytes)
+        step_kernels = S.last_kernels()
+        S.set_arith(arith_read)
+        A1d, A2d, A3d = (zeros(n) for n in act_sizes(cfg, size, size, batch))
+        S.train_activations(net, size, size, batch, ws, nbytes, A1d, A2d, A3d)
+        assert ran_x6(step_kernels) == (arith_step == 0), step_kernels
+        assert_close(H(A1d), A1ref, RTOL, "A1 (step arith %d, read under %d)" % (arith_step, arith_read))
 
 
 @pytest.mark.parametrize("arith", [0, 1], ids=["split", "f32"])
@@ -614,7 +565,6 @@ def test_train_step_sq_err_and_a3_vs_oracle(S, name, batch, w, h, l3, arith):
     workspace (srcnn_train_activations) against the oracle
     (last_layer_delta.cl, squared_error.cl, layer_deltas.cl, backpropagate.cl)."""
     cfg = NETS[name]
-    net = S.Net(*cfg)
     rng = np.random.default_rng(31)
     X, T = make_batch(rng, batch, w, h)
     params = make_params(rng, cfg, sd=0.05)
@@ -622,39 +572,24 @@ def test_train_step_sq_err_and_a3_vs_oracle(S, name, batch, w, h, l3, arith):
     g0 = (1e-3 * rng.standard_normal(P)).astype(np.float32)
     rg, _ = orc.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
     xg, _ = orc.f64.train_fwd_bwd(cfg, X, T, w, h, batch, params, g0)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g, err = D(g0), zeros(1)
-    S.set_arith(arith)
-    try:
-        S.train_fwd_bwd(net, D(X), D(T), w, h, batch, D(params), g, err, ws, nbytes)
-    finally:
-        S.set_arith(0)
-    assert S.last_path() == "fused", S.last_path()
-    ks = S.last_kernels()
+    st = run_step(S, cfg, w, h, batch, X, T, params, g0, arith=arith)
+    S.set_arith(0)
+    assert st.path == "fused", st.path
+    ks = st.kernels
     if l3 == "l3r":
-        x6 = any("x6" in k for k in ks)
+        x6 = ran_x6(ks)
         assert x6 == (arith == 0), ks
         want = ["l3r_d3", "d1x6_d3"] if x6 else ["l3r_delta"]
         assert all(k in ks for k in want), ks
     else:
         assert l3 in ks, ks
         assert "l3r_d3" not in ks and "d1x6_d3" not in ks, ks
-    got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "l3 grad %s" % nm, xg[sl], FLIP_FLOOR)
-    pad = cfg[2] + cfg[3] + cfg[4] - 3
+    check_gradients(cfg, st.grads, rg, xg, "l3 ")
+    w3, h3 = dims(cfg, w, h)[4:]
     A3 = orc.forward(cfg, X, w, h, batch, params)
-    ref_err = orc.sq_err(T, A3, w, h, w - pad, h - pad, batch)
-    assert float(H(err)[0]) == pytest.approx(ref_err, rel=1e-4)
-    n1, n2 = cfg[0], cfg[1]
-    w1, h1 = w - cfg[2] + 1, h - cfg[2] + 1
-    w3, h3 = w1 - cfg[4] + 1, h1 - cfg[4] + 1
-    A1d, A2d, A3d = zeros(batch * w1 * h1 * n1), zeros(batch * w1 * h1 * n2), zeros(batch * w3 * h3)
-    S.train_activations(net, w, h, batch, ws, nbytes, A1d, A2d, A3d)
-    assert_close(H(A3d), A3, RTOL, "l3 A3")
+    ref_err = orc.sq_err(T, A3, w, h, w3, h3, batch)
+    assert st.sq_err == pytest.approx(ref_err, rel=1e-4)
+    assert_close(st.activations()[2], A3, RTOL, "l3 A3")
 
 
 def test_forward_vs_oracle(S, path):
@@ -730,14 +665,11 @@ def test_forward_large_frame_fused_vs_generic(S):
     res = {}
     for p in (0, 1):
         S.set_path(p)
-        try:
-            nbytes = S.forward_workspace_bytes(net, w, h, 1)
-            ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-            out = torch.full((n_out,), float("nan"), dtype=torch.float32, device="cuda")
-            S.forward(net, D(X), w, h, 1, D(params), out, ws, nbytes)
-            res[p] = H(out)
-        finally:
-            S.set_path(0)
+        nbytes = S.forward_workspace_bytes(net, w, h, 1)
+        ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
+        out = torch.full((n_out,), float("nan"), dtype=torch.float32, device="cuda")
+        S.forward(net, D(X), w, h, 1, D(params), out, ws, nbytes)
+        res[p] = H(out)
     assert np.isfinite(res[0]).all()
     ref = orc.forward(cfg, X, w, h, 1, params)
     ref64 = orc.f64.forward(cfg, X, w, h, 1, params)
@@ -799,10 +731,7 @@ def test_full_batch_gradients_vs_oracle(S):
     g = zeros(P)
     S.train_fwd_bwd(net, Xd, Td, size, size, batch, pd, g, None, ws, nbytes)
     got = H(g)
-    off = S.net_offsets(net) + [P]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], rg[sl], RTOL, "full-batch grad " + nm, xg[sl], FLIP_FLOOR)
+    check_gradients(cfg, got, rg, xg, "full-batch ")
     # determinism: a second pass gives bit-identical gradients
     g2 = zeros(P)
     S.train_fwd_bwd(net, Xd, Td, size, size, batch, pd, g2, None, ws, nbytes)

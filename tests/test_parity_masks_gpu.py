@@ -18,7 +18,7 @@ bound), and at most a handful per array may pass by that clause alone
 (hip_util.MAX_ROUND_ONLY), so an accumulation regression cannot hide there.
 
 Each flip is also checked to be a genuine rounding case: its exact
-pre-activation lies within AMBIG x (sum of the absolute values of its terms)
+pre-activation lies within step_util.AMBIG x (sum of the absolute values of its terms)
 of zero.  The last layer's ReLU' (the quirk of last_layer_delta.cl:45) is taken from
 the HIP path's A3 the same way.
 
@@ -32,94 +32,12 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-from hip_util import RTOL, assert_close, log_record, make_batch, make_params
+from hip_util import NAMES, RTOL, act_sizes, assert_close, dims, log_record, make_batch, make_params, offsets, segments
+from step_util import S, _settings, check_flips, decisions, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 NETS = {"default": (64, 32, 9, 1, 5), "example": (32, 16, 9, 1, 5), "wide": (128, 64, 9, 5, 5)}
-# a decision is ambiguous when |exact pre-activation| <= AMBIG x sum |terms|:
-# far above fp32's unit roundoff times the term count of any layer here
-# (<= 3201 terms x 6e-8 = 2e-4 worst case, ~1e-6 typical), far below the
-# activations' own spread
-AMBIG = 1e-5
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def dims(cfg, w, h):
-    n1, n2, f1, f2, f3 = cfg
-    w1, h1 = w - f1 + 1, h - f1 + 1
-    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
-    return w1, h1, w2, h2, w2 - f3 + 1, h2 - f3 + 1
-
-
-def hip_step(S, cfg, X, T, w, h, batch, params, g0):
-    """srcnn_train_fwd_bwd, then the activations it left in the workspace."""
-    net = S.Net(*cfg)
-    w1, h1, w2, h2, _, _ = dims(cfg, w, h)
-    nbytes = S.train_workspace_bytes(net, w, h, batch)
-    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g = D(g0)
-    S.train_fwd_bwd(net, D(X), D(T), w, h, batch, D(params), g, None, ws, nbytes)
-    path = S.last_path()
-    w3, h3 = dims(cfg, w, h)[4:]
-    A1 = torch.empty(batch * w1 * h1 * cfg[0], dtype=torch.float32, device="cuda")
-    A2 = torch.empty(batch * w2 * h2 * cfg[1], dtype=torch.float32, device="cuda")
-    A3 = torch.empty(batch * w3 * h3, dtype=torch.float32, device="cuda")
-    S.train_activations(net, w, h, batch, ws, nbytes, A1, A2, A3)
-    return H(g), H(A1), H(A2), H(A3), path
-
-
-def split(cfg, params):
-    n1, n2, f1, f2, f3 = cfg
-    sizes = [f1 * f1 * n1, n1, f2 * f2 * n1 * n2, n2, f3 * f3 * n2, 1]
-    out, o = [], 0
-    for s in sizes:
-        out.append(params[o:o + s])
-        o += s
-    return out
-
-
-def decisions(cfg, X, w, h, batch, params, A1m):
-    """Exact (f64) pre-activations of layers 1 and 2 and the sums of the
-    absolute values of their terms; layer 2 is fed the masked exact A1."""
-    n1, n2, f1, f2, f3 = cfg
-    W1, B1, W2, B2, W3, B3 = split(cfg, np.asarray(params, np.float64))
-    w1, h1, w2, h2, _, _ = dims(cfg, w, h)
-    F = orc.f64
-    pre1 = F.conv_fwd(X, W1, B1, w, h, 1, n1, f1, 0, batch)
-    mag1 = F.conv_fwd(np.abs(X), np.abs(W1), np.abs(B1), w, h, 1, n1, f1, 0, batch)
-    pre2 = F.conv_fwd(A1m, W2, B2, w1, h1, n1, n2, f2, 0, batch)
-    mag2 = F.conv_fwd(np.abs(A1m), np.abs(W2), np.abs(B2), w1, h1, n1, n2, f2, 0, batch)
-    return pre1, mag1, pre2, mag2
-
-
-def check_flips(what, mask, pre, mag):
-    """Every HIP decision that differs from the exact one is a rounding case."""
-    exact = pre > 0
-    flips = mask != exact
-    amb = np.abs(pre) <= AMBIG * mag
-    n_flip, n_amb = int(flips.sum()), int(amb.sum())
-    bad = int((flips & ~amb).sum())
-    assert bad == 0, "%s: %d ReLU decisions differ from the exact sign outside the rounding band" % (what, bad)
-    return n_flip, n_amb
 
 
 def sample_partials(cfg, X, w, h, batch, acts):
@@ -166,7 +84,9 @@ def masked_parity(S, cfg, name, X, T, w, h, batch, params, g0, rep=1):
     n1, n2, f1, f2, f3 = cfg
     w1, h1, w2, h2, w3, h3 = dims(cfg, w, h)
     Xb, Tb = (np.tile(X, rep), np.tile(T, rep)) if rep > 1 else (X, T)
-    got, A1, A2, A3h, path = hip_step(S, cfg, Xb, Tb, w, h, batch * rep, params, g0)
+    st = run_step(S, cfg, w, h, batch * rep, Xb, Tb, params, g0, sq_err=False)
+    got, path = st.grads, st.path
+    A1, A2, A3h = st.activations()
     m1, m2, m3 = A1 > 0, A2 > 0, A3h > 0
     if rep > 1:
         ms = [m.reshape(rep, -1) for m in (m1, m2, m3)]
@@ -179,9 +99,9 @@ def masked_parity(S, cfg, name, X, T, w, h, batch, params, g0, rep=1):
     assert np.abs(xg_m).max() > 0, "degenerate case: every gradient is zero"
     xg_m = rep * xg_m + g0
     # every differing decision lies in the rounding band of its exact value
-    s1, s2, s3 = batch * w1 * h1 * n1, batch * w2 * h2 * n2, batch * w3 * h3
+    s1, s2, s3 = act_sizes(cfg, w, h, batch)
     pre1, mag1, pre2, mag2 = decisions(cfg, X, w, h, batch, params, xacts[:s1])
-    W1, B1, W2, B2, W3, B3 = split(cfg, np.asarray(params, np.float64))
+    W1, B1, W2, B2, W3, B3 = segments(cfg, np.asarray(params, np.float64))
     pre3 = xacts[s1 + s2:s1 + s2 + s3]
     mag3 = orc.f64.conv_fwd(np.abs(xacts[s1:s1 + s2]), np.abs(W3), np.abs(B3), w2, h2, n2, 1, f3, 0, batch)
     flips = [check_flips("%s A%d" % (name, k + 1), m, p, mg)
@@ -197,8 +117,8 @@ def masked_parity(S, cfg, name, X, T, w, h, batch, params, g0, rep=1):
     else:
         ref32 = sequential_f32_sum(sample_partials(cfg, X, w, h, batch, xacts), rep, g0)
     mag, nterms = term_magnitudes(cfg, X, w, h, batch, xacts, rep, g0)
-    off = np.cumsum([0] + [p.size for p in split(cfg, params)])
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
+    off = offsets(cfg)
+    for i, nm in enumerate(NAMES):
         sl = slice(off[i], off[i + 1])
         assert_close(got[sl], ref32[sl], RTOL, "%s masked grad %s (%s, b%d x%d)" % (name, nm, path, batch, rep),
                      xg_m[sl], abs_floor=0.0, mag=mag[sl], nterms=nterms[i // 2])
@@ -211,7 +131,7 @@ def term_magnitudes(cfg, X, w, h, batch, xacts, rep, g0):
     the accumulated g0) and, per layer, the number of those terms."""
     n1, n2, f1, f2, f3 = cfg
     w1, h1, w2, h2, w3, h3 = dims(cfg, w, h)
-    s1, s2, s3 = batch * w1 * h1 * n1, batch * w2 * h2 * n2, batch * w3 * h3
+    s1, s2, s3 = act_sizes(cfg, w, h, batch)
     o = np.cumsum([0, s1, s2, s3, s3, s2, s1])
     A1, A2 = np.abs(xacts[o[0]:o[1]]), np.abs(xacts[o[1]:o[2]])
     D3, D2, D1 = np.abs(xacts[o[3]:o[4]]), np.abs(xacts[o[4]:o[5]]), np.abs(xacts[o[5]:o[6]])
@@ -238,10 +158,7 @@ def test_gradients_under_hip_relu_decisions(S, path, name, batch, size):
     params = make_params(rng, cfg, sd=0.05)
     g0 = (1e-3 * rng.standard_normal(params.size)).astype(np.float32)
     S.set_path(path)
-    try:
-        masked_parity(S, cfg, name, X, T, size, size, batch, params, g0)
-    finally:
-        S.set_path(0)
+    masked_parity(S, cfg, name, X, T, size, size, batch, params, g0)
 
 
 def test_full_batch_gradients_under_hip_relu_decisions(S):

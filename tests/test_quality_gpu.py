@@ -30,7 +30,8 @@ import pytest
 import hip_util
 import quality_ref as Q
 from conftest import ROOT
-from hip_util import guarded, guards_intact, make_params
+from hip_util import H, guarded, guards_intact, make_params
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -39,29 +40,6 @@ torch = pytest.importorskip("torch")
 CNN = os.path.join(ROOT, "cnn-super-resolution_amd", "bin", "cnn")
 NETS = {"default": (64, 32, 9, 1, 5), "wide": (128, 64, 9, 5, 5)}
 INF = float("inf")
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 def fmt_of(img):

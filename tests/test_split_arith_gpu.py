@@ -11,37 +11,13 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-from hip_util import log_record, make_batch, make_params
+from hip_util import D, H, NAMES, log_record, make_batch, make_params, normwise, ran_x6, segments
+from step_util import S, _settings, run_step  # noqa: F401
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 NET = (64, 32, 9, 1, 5)
-NAMES = ["W1", "B1", "W2", "B2", "W3", "B3"]
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    yield srcnn_amd
-    srcnn_amd.set_arith(0)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def normwise(got, ref64):
-    got = np.asarray(got, np.float64)
-    ref64 = np.asarray(ref64, np.float64)
-    return float(np.linalg.norm(got - ref64) / max(np.linalg.norm(ref64), 1e-300))
 
 
 def workspace(S, net, size, batch):
@@ -49,16 +25,6 @@ def workspace(S, net, size, batch):
     both), so the tests query once and run both on the same workspace."""
     nbytes = S.train_workspace_bytes(net, size, size, batch)
     return torch.empty(nbytes // 4 + 64, dtype=torch.float32, device="cuda"), nbytes
-
-
-def grads(S, arith, X, T, size, batch, params, g0, wsn):
-    S.set_arith(arith)
-    net = S.Net(*NET)
-    ws, nbytes = wsn
-    g = D(g0)
-    err = torch.zeros(1, dtype=torch.float32, device="cuda")
-    S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), g, err, ws, nbytes)
-    return H(g), S.last_kernels()
 
 
 @pytest.mark.parametrize("batch,size,sd", [(64, 33, 0.05), (600, 33, 0.05), (256, 33, 1e-3), (7, 25, 0.05)])
@@ -71,15 +37,13 @@ def test_split_arith_within_fp32_error(S, batch, size, sd):
     g32, _ = orc.train_fwd_bwd(NET, X, T, size, size, batch, params, g0)
     g64, _ = orc.f64.train_fwd_bwd(NET, X, T, size, size, batch, params, g0)
     wsn = workspace(S, S.Net(*NET), size, batch)
-    gs, ks = grads(S, 0, X, T, size, batch, params, g0, wsn)
-    gf, kf = grads(S, 1, X, T, size, batch, params, g0, wsn)
+    split, f32 = (run_step(S, NET, size, size, batch, X, T, params, arith=arith, ws=wsn) for arith in (0, 1))
+    ks, kf = split.kernels, f32.kernels
     # (l3r writes delta3 and d1x6 forms delta2 where l3r serves the tile)
     assert "l12x6_fwd" in ks and any(k in ks for k in ("d1x6_grad12", "d1x6_d3")), ks
-    assert "l12_fwd" in kf and "x6" not in kf, kf
-    off = S.net_offsets(S.Net(*NET)) + [P]
-    for i, nm in enumerate(NAMES):
-        sl = slice(off[i], off[i + 1])
-        es, ef, eo = normwise(gs[sl], g64[sl]), normwise(gf[sl], g64[sl]), normwise(g32[sl], g64[sl])
+    assert "l12_fwd" in kf and not ran_x6(kf), kf
+    for nm, gs, gf, go, gx in zip(NAMES, *(segments(NET, g) for g in (split.grads, f32.grads, g32, g64))):
+        es, ef, eo = normwise(gs, gx), normwise(gf, gx), normwise(go, gx)
         log_record({"test": "split_arith", "batch": batch, "size": size, "sd": sd, "seg": nm,
                     "err_split": es, "err_f32_mfma": ef, "err_f32_oracle": eo})
         print("%s batch %d: split %.3e  fp32 MFMA %.3e  fp32 oracle %.3e" % (nm, batch, es, ef, eo))
@@ -129,22 +93,12 @@ def test_split_wide_within_fp32_error(S, batch, size):
     g0 = np.zeros(P, np.float32)
     g64, _ = orc.f64.train_fwd_bwd(WIDE, X, T, size, size, batch, params, g0)
     g32, _ = orc.train_fwd_bwd(WIDE, X, T, size, size, batch, params, g0)
-    res = {}
-    net = S.Net(*WIDE)
-    ws, nbytes = workspace(S, net, size, batch)
-    for arith in (0, 1):
-        S.set_arith(arith)
-        g = D(g0)
-        err = torch.zeros(1, dtype=torch.float32, device="cuda")
-        S.train_fwd_bwd(net, D(X), D(T), size, size, batch, D(params), g, err, ws, nbytes)
-        res[arith] = (H(g), S.last_kernels())
-    assert all(k in res[0][1] for k in ("wl1x6_fwd", "wl2x6_fwd", "wd1x6", "wg1x6", "wgrad2x6")), res[0][1]
-    assert "x6" not in res[1][1], res[1][1]
-    off = S.net_offsets(S.Net(*WIDE)) + [P]
-    for i, nm in enumerate(NAMES):
-        sl = slice(off[i], off[i + 1])
-        es, ef = normwise(res[0][0][sl], g64[sl]), normwise(res[1][0][sl], g64[sl])
-        eo = normwise(g32[sl], g64[sl])
+    wsn = workspace(S, S.Net(*WIDE), size, batch)
+    split, f32 = (run_step(S, WIDE, size, size, batch, X, T, params, arith=arith, ws=wsn) for arith in (0, 1))
+    assert all(k in split.kernels for k in ("wl1x6_fwd", "wl2x6_fwd", "wd1x6", "wg1x6", "wgrad2x6")), split.kernels
+    assert not ran_x6(f32.kernels), f32.kernels
+    for nm, gs, gf, go, gx in zip(NAMES, *(segments(WIDE, g) for g in (split.grads, f32.grads, g32, g64))):
+        es, ef, eo = normwise(gs, gx), normwise(gf, gx), normwise(go, gx)
         log_record({"test": "split_wide", "batch": batch, "size": size, "seg": nm, "err_split": es,
                     "err_f32_mfma": ef, "err_f32_oracle": eo})
         print("wide %s batch %d size %d: split %.3e  fp32 MFMA %.3e  fp32 oracle %.3e" % (nm, batch, size, es, ef, eo))

@@ -14,7 +14,8 @@ import pytest
 import hip_util
 import upscale_ref as U
 from conftest import ROOT
-from hip_util import guarded, guards_intact, make_params, same_bits
+from hip_util import H, guarded, guards_intact, make_params, same_bits
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,29 +38,6 @@ PADS = [0, 7, 12]  # 7: the odd margin (3 left / top, 4 right / bottom)
 # the reference's channel values lie within 2e-3 of an integer; seeds 0 - 2
 # put 2 such values among the 72 - 162 of a tiny case.
 RGBA_SEED, LUMA_SEED = 0, 3
-
-
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 import srcnn_oracle as orc
-import test_parity_masks_gpu as masks
-from hip_util import FLIP_FLOOR, RTOL, assert_close, make_batch, make_params
-from test_parity_masks_gpu import dims
+from hip_util import (FLIP_FLOOR, H, NAMES, RTOL, act_sizes, assert_close, check_gradients, dims, make_batch,
+                      make_params, offsets, segments)
+from step_util import S, _settings, check_flips, decisions, run_step  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,64 +23,37 @@ torch = pytest.importorskip("torch")
 WIDE = (128, 64, 9, 5, 5)
 
 
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    srcnn_amd.set_path(0)
-    return srcnn_amd
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
 def align(n):
     return (n + 255) & ~255
 
 
-def run_step(S, w, h, batch, seed, sd=0.05, g0=None, want_acts=False):
+def wide_step(S, w, h, batch, seed, sd=0.05, g0=None, want_acts=False):
+    """The step on seeded inputs, a zero-filled workspace (read back whole for
+    split_ws) and the profile on."""
     net = S.Net(*WIDE)
     rng = np.random.default_rng(seed)
     X, T = make_batch(rng, batch, w, h)
     params = make_params(rng, WIDE, sd=sd)
-    P = params.size
     if g0 is None:
-        g0 = np.zeros(P, np.float32)
+        g0 = np.zeros(params.size, np.float32)
     nbytes = S.train_workspace_bytes(net, w, h, batch)
     ws = torch.zeros(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g = D(g0)
-    err = torch.zeros(1, dtype=torch.float32, device="cuda")
     S.profile_reset()
     S.profile_enable(True)
-    S.train_fwd_bwd(net, D(X), D(T), w, h, batch, D(params), g, err, ws, nbytes)
-    torch.cuda.synchronize()
+    st = run_step(S, WIDE, w, h, batch, X, T, params, g0, ws=(ws, nbytes))
     S.profile_enable(False)
-    stats = S.profile_stats()
-    out = (X, T, params, g0, H(g), float(H(err)[0]), H(ws), stats)
+    out = (X, T, params, g0, st.grads, st.sq_err, H(ws), S.profile_stats())
     if want_acts:
         # the activations the step left (srcnn_train_activations): its own
         # ReLU decisions
-        w1, h1, w2, h2, w3, h3 = dims(WIDE, w, h)
-        A1 = torch.empty(batch * w1 * h1 * WIDE[0], dtype=torch.float32, device="cuda")
-        A2 = torch.empty(batch * w2 * h2 * WIDE[1], dtype=torch.float32, device="cuda")
-        A3 = torch.empty(batch * w3 * h3, dtype=torch.float32, device="cuda")
-        S.train_activations(net, w, h, batch, ws, nbytes, A1, A2, A3)
-        out += ((H(A1), H(A2), H(A3)),)
+        out += (tuple(st.activations()),)
     return out
 
 
 def split_ws(ws, w, h, batch):
-    n1, n2, f1, f2, f3 = WIDE
-    w1, h1 = w - f1 + 1, h - f1 + 1
-    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
-    s1, s2 = w1 * h1 * n1 * batch, w2 * h2 * n2 * batch
+    n1 = WIDE[0]
+    w1, h1 = dims(WIDE, w, h)[:2]
+    s1, s2 = act_sizes(WIDE, w, h, batch)[:2]
     # the A1 region holds whole 32-pixel chunks per sample (abi.cpp NetDims::s1p)
     s1p = (w1 * h1 + 31) // 32 * 32 * n1 * batch
     o = 0
@@ -97,16 +70,14 @@ def split_ws(ws, w, h, batch):
 @pytest.mark.parametrize("w,h,batch", [(33, 33, 1), (33, 33, 6), (29, 29, 3), (33, 27, 2),
                                        (25, 31, 3), (33, 33, 8)])
 def test_wide_step_stages_vs_oracle(S, w, h, batch):
-    X, T, params, g0, got, err, ws, stats, hacts = run_step(S, w, h, batch, seed=7 + w + h + batch,
+    X, T, params, g0, got, err, ws, stats, hacts = wide_step(S, w, h, batch, seed=7 + w + h + batch,
                                                             want_acts=True)
     assert "wide_l2_fwd" in stats and "wide_grad2" in stats, stats.keys()
     ref_g, acts = orc.train_fwd_bwd(WIDE, X, T, w, h, batch, params, g0, want_acts=True)
     x_g, xacts = orc.f64.train_fwd_bwd(WIDE, X, T, w, h, batch, params, g0, want_acts=True)
     n1, n2, f1, f2, f3 = WIDE
-    w1, h1 = w - f1 + 1, h - f1 + 1
-    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
-    w3, h3 = w2 - f3 + 1, h2 - f3 + 1
-    s1, s2, s3 = w1 * h1 * n1 * batch, w2 * h2 * n2 * batch, w3 * h3 * batch
+    w1, h1, w2, h2, w3, h3 = dims(WIDE, w, h)
+    s1, s2, s3 = act_sizes(WIDE, w, h, batch)
     rA1 = acts[:s1]
     rA2 = acts[s1:s1 + s2]
     rD2 = acts[s1 + s2 + 2 * s3:s1 + 2 * s2 + 2 * s3]
@@ -120,22 +91,18 @@ def test_wide_step_stages_vs_oracle(S, w, h, batch):
     # |exact| = 1.7e-8 of its terms' magnitude, under the split-bf16 L1) and
     # its whole delta then enters the gradients, far past FLIP_FLOOR; every
     # decision that differs from the exact sign must lie in the rounding band
-    # (test_parity_masks_gpu.check_flips)
+    # (step_util.check_flips)
     m1, m2, m3 = (a > 0 for a in hacts)
     ref_m, _ = orc.train_fwd_bwd_masked(WIDE, X, T, w, h, batch, params, g0, m1, m2, m3)
     x_m, xacts_m = orc.f64.train_fwd_bwd_masked(WIDE, X, T, w, h, batch, params, np.asarray(g0, np.float64),
                                                 m1, m2, m3, want_acts=True)
-    pre1, mag1, pre2, mag2 = masks.decisions(WIDE, X, w, h, batch, params, xacts_m[:s1])
-    W3_, B3_ = masks.split(WIDE, np.asarray(params, np.float64))[4:]
+    pre1, mag1, pre2, mag2 = decisions(WIDE, X, w, h, batch, params, xacts_m[:s1])
+    W3_, B3_ = segments(WIDE, np.asarray(params, np.float64))[4:]
     pre3 = xacts_m[s1 + s2:s1 + s2 + s3]
     mag3 = orc.f64.conv_fwd(np.abs(xacts_m[s1:s1 + s2]), np.abs(W3_), np.abs(B3_), w2, h2, n2, 1, f3, 0, batch)
     for k, (m, p, mg) in enumerate(((m1, pre1, mag1), (m2, pre2, mag2), (m3, pre3, mag3))):
-        masks.check_flips("wide A%d" % (k + 1), m, p, mg)
-    net = S.Net(*WIDE)
-    off = S.net_offsets(net) + [params.size]
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
-        sl = slice(off[i], off[i + 1])
-        assert_close(got[sl], ref_m[sl], RTOL, "grad " + nm, x_m[sl], FLIP_FLOOR)
+        check_flips("wide A%d" % (k + 1), m, p, mg)
+    check_gradients(WIDE, got, ref_m, x_m, "")
     A3 = orc.forward(WIDE, X, w, h, batch, params)
     ref_err = orc.sq_err(T, A3, w, h, w3, h3, batch)
     assert err == pytest.approx(ref_err, rel=1e-4)
@@ -146,23 +113,20 @@ def test_wide_step_accumulates_and_is_deterministic(S):
     batch = 300
     rng = np.random.default_rng(3)
     g0 = (1e-3 * rng.standard_normal(orc.param_count(*WIDE))).astype(np.float32)
-    X, T, params, _, got, _, _, _ = run_step(S, w, h, batch, seed=11, g0=g0)
+    X, T, params, _, got, _, _, _ = wide_step(S, w, h, batch, seed=11, g0=g0)
     ref_g, _ = orc.train_fwd_bwd(WIDE, X, T, w, h, batch, params, g0)
     x_g, _ = orc.f64.train_fwd_bwd(WIDE, X, T, w, h, batch, params, g0)
     assert_close(got, ref_g, RTOL, "wide gradients (accumulated onto g0)", x_g, FLIP_FLOOR)
-    _, _, _, _, got2, _, _, _ = run_step(S, w, h, batch, seed=11, g0=g0)
+    _, _, _, _, got2, _, _, _ = wide_step(S, w, h, batch, seed=11, g0=g0)
     np.testing.assert_array_equal(got2, got)
 
 
 def test_wide_fast_matches_generic_path(S):
     w = h = 33
     batch = 64
-    fast = run_step(S, w, h, batch, seed=5)
+    fast = wide_step(S, w, h, batch, seed=5)
     S.set_path(1)
-    try:
-        gen = run_step(S, w, h, batch, seed=5)
-    finally:
-        S.set_path(0)
+    gen = wide_step(S, w, h, batch, seed=5)
     assert "wide_l2_fwd" not in gen[7]
     assert_close(fast[4], gen[4], RTOL, "fast vs generic gradients")
     assert fast[5] == pytest.approx(gen[5], rel=1e-4)
@@ -186,27 +150,22 @@ def test_wide_full_batch_4096_vs_oracle(S):
     Xb, Tb = np.tile(X, rep), np.tile(T, rep)
     nbytes = S.train_workspace_bytes(net, w, h, batch)
     ws = torch.zeros(nbytes // 4 + 64, dtype=torch.float32, device="cuda")
-    g = torch.zeros(P, dtype=torch.float32, device="cuda")
-    S.train_fwd_bwd(net, D(Xb), D(Tb), w, h, batch, D(params), g, None, ws, nbytes)
-    assert S.last_path() == "wide"
-    got = H(g)
+    step = run_step(S, WIDE, w, h, batch, Xb, Tb, params, sq_err=False, ws=(ws, nbytes))
+    assert step.path == "wide"
+    got = step.grads
     ref_g, acts = orc.train_fwd_bwd(WIDE, X, T, w, h, distinct, params, np.zeros(P, np.float32),
                                     want_acts=True)
     x_g, xacts = orc.f64.train_fwd_bwd(WIDE, X, T, w, h, distinct, params, np.zeros(P), want_acts=True)
-    off = S.net_offsets(net) + [P]
+    off = offsets(WIDE)
     # 2.6M-term fp32 sums (64x the oracle's 64-tile sums): 2e-4 normwise, as
     # for the other >1M-term sums (test_backpropagation_big_data), and the
     # same as the elementwise floor (7M ReLU decisions of A1 / A2 feed these
     # gradients, so a few fall within fp32 rounding of zero, hip_util.FLIP_FLOOR)
-    for i, nm in enumerate(["W1", "B1", "W2", "B2", "W3", "B3"]):
+    for i, nm in enumerate(NAMES):
         sl = slice(off[i], off[i + 1])
         assert_close(got[sl], rep * ref_g[sl], 2e-4, "batch-4096 grad " + nm, rep * x_g[sl], 2e-4)
     # sampled activation slices: tiles 0, 1000, 4095 (sources 0, 1000 % 64, 63)
-    n1, n2, f1, f2, f3 = WIDE
-    w1, h1 = w - f1 + 1, h - f1 + 1
-    w2, h2 = w1 - f2 + 1, h1 - f2 + 1
-    w3, h3 = w2 - f3 + 1, h2 - f3 + 1
-    s1, s2, s3 = w1 * h1 * n1, w2 * h2 * n2, w3 * h3
+    s1, s2, s3 = act_sizes(WIDE, w, h, 1)
     a2 = slice(s1 * distinct, (s1 + s2) * distinct)
     d2 = slice((s1 + s2 + 2 * s3) * distinct, (s1 + 2 * s2 + 2 * s3) * distinct)
     st = split_ws(H(ws), w, h, batch)

@@ -20,7 +20,8 @@ import pytest
 import hip_util
 import yuv_deep_ref as D
 from conftest import ROOT
-from hip_util import guarded, guards_intact, make_params
+from hip_util import H, guarded, guards_intact, make_params
+from step_util import S, _settings  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -49,31 +50,8 @@ COMPOSE_EXEMPT = {10: 0.0025, 12: 0.005, 16: 0.07}
 COMPOSE_SEEDS = {10: 0, 12: 0, 16: 2}
 
 
-@pytest.fixture(scope="module")
-def S():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import srcnn_amd
-    return srcnn_amd
-
-
-@pytest.fixture(autouse=True)
-def _settings(S):
-    try:
-        yield
-    finally:
-        S.set_arith(0)
-        S.set_path(0)
-        hip_util._GUARDS.clear()
-
-
 def rng_code(S, r):
     return S.YUV_FULL if r == D.FULL else S.YUV_LIMITED
-
-
-def H(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 def nbytes_of(bits):
