@@ -36,8 +36,11 @@
 //          tile 4 holds row 8 and column 8 (rows 0-6), tap (7,8) goes to VALU
 //   pixel -> X offset table (ints, one per pixel slot of the sample): the 4
 //          offsets of a lane's k-steps are one ds_read_b128 per pixel tile
-// M0 is written by the DMA asm only; the compiler sets it itself around its own uses
-#pragma clang diagnostic ignored "-Winline-asm"
+// The DMAs are lds_dma.hpp's inline asm (why not the builtin: there);
+// consumers reach DMA'd data through the explicit wait + barrier.
+using lds_dma::dma16;
+using lds_dma::dma16s;
+using lds_dma::dma4s;
 
 // 4-wave teams per block, on alternate chunks of a sample (two teams per
 // block, 512 slabs instead of 1024: d1 0.4065 vs 0.399 ms)
@@ -48,28 +51,6 @@ constexpr int kD1cS = 40;       // X tile row stride in LDS (8 mod 32)
 constexpr int kD1cMaxPx = 1024; // pixel slots of the X offset table (nch * 32)
 
 __device__ float g_d1c_zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // 16-B zero source (delta2 rows past the sample)
-
-// LDS-DMA as inline asm (train_wide.hip, dma16): through the builtin the
-// compiler puts an s_waitcnt vmcnt(0) before later LDS reads of the current
-// buffer; consumers reach DMA'd data through the explicit wait + barrier.
-__device__ __forceinline__ uint32_t d1c_m0(const float* lds_dst) {
-  return __builtin_amdgcn_readfirstlane(
-      (uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) void*)lds_dst));
-}
-// 16 B per lane from a 64-bit per-lane address
-__device__ __forceinline__ void d1c_dma16v(const float* src, float* lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
-               : : "s"(d1c_m0(lds_dst)), "v"(src) : "m0");
-}
-// 16 B per lane from a wave-uniform base + 32-bit per-lane byte offset
-__device__ __forceinline__ void d1c_dma16s(const float* base, uint32_t off, float* lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-               : : "s"(d1c_m0(lds_dst)), "v"(off), "s"(base) : "m0");
-}
-__device__ __forceinline__ void d1c_dma4s(const float* base, uint32_t off, float* lds_dst) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2"
-               : : "s"(d1c_m0(lds_dst)), "v"(off), "s"(base) : "m0");
-}
 
 inline bool d1c_fits(int w, int h) { return w <= kD1cS && ((w - 8) * (h - 8) + 31) / 32 * 32 <= kD1cMaxPx; }
 inline int d1c_xs_floats(int h) { return (kD1cS * h + 63) / 64 * 64; }
@@ -157,16 +138,16 @@ __global__ __launch_bounds__(256 * kD1cTeams, kD1cOcc) void d1c_grad12_kernel(co
   auto dma_chunk = [&](int smp, int c, int b) {
     const float* a1c = A1 + ((size_t)smp * nch + c) * (32 * N1);
 #pragma unroll
-    for (int k = 0; k < 2; k++) d1c_dma16s(a1c, a1off[k], a1i + (b * 4 + wave) * 512 + 256 * k);
+    for (int k = 0; k < 2; k++) dma16s(a1c, a1off[k], a1i + (b * 4 + wave) * 512 + 256 * k);
     const float* d2c = D2 + ((size_t)smp * npx + c * 32) * N2;
     float* dst = d2i + b * 1024 + 256 * wave;
     if (c * 32 + 32 <= npx) {
-      d1c_dma16s(d2c, d2off, dst);
+      dma16s(d2c, d2off, dst);
     } else {  // the sample's last chunk: rows past it read zeros
       int l_ = lane;
       asm volatile("" : "+v"(l_));
       const int p = (64 * wave + l_) >> 3;
-      d1c_dma16v(c * 32 + p < npx ? d2c + d2off / 4 : g_d1c_zero, dst);
+      dma16(c * 32 + p < npx ? d2c + d2off / 4 : g_d1c_zero, dst);
     }
   };
   // X tile of sample smp -> dst at row stride S (pad slots read a clamped pixel)
@@ -176,7 +157,7 @@ __global__ __launch_bounds__(256 * kD1cTeams, kD1cOcc) void d1c_grad12_kernel(co
       int l_ = lane;
       asm volatile("" : "+v"(l_));
       const int f = 64 * k + l_, r = f / S;
-      d1c_dma4s(xsrc, 4u * (min(r, g.H - 1) * g.W + min(f - r * S, g.W - 1)), dst + 64 * k);
+      dma4s(xsrc, 4u * (min(r, g.H - 1) * g.W + min(f - r * S, g.W - 1)), dst + 64 * k);
     }
   };
 

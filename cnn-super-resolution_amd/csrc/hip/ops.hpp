@@ -195,10 +195,11 @@ int preload_forward(const srcnn_net* net);
 int forward_clock(double* ghz);
 }  // namespace fused
 
-// Training step for nets with a spatial middle layer (train_wide.hip), e.g.
-// the wide config n1=128, n2=64, f1=9, f2=5, f3=5: per-stage MFMA kernels over
-// the reference-layout A1 / D1 / A2 / D2 buffers (A1 in kA1Hwc; b.D3 is not
-// used).  Same contracts as fused::train_plan (WidePlan) and
+// Training step for nets with a spatial middle layer (train_wide.hip; one
+// header per kernel family, wl1.hpp .. wgrad2x6.hpp), e.g. the wide config
+// n1=128, n2=64, f1=9, f2=5, f3=5: per-stage MFMA kernels over the
+// reference-layout A1 / D1 / A2 / D2 buffers (A1 in kA1Hwc; b.D3 is not used).
+// Same contracts as fused::train_plan (WidePlan, wide_plan.hpp) and
 // fused::train_fwd_bwd; with `up` the update always rides along (returns 2).
 namespace wide {
 bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, StepNeed* need);

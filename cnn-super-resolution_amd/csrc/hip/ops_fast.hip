@@ -28,9 +28,10 @@
 //                       channels of one pixel: 16-B stores
 //     l1_grad_kernel    gW1 (+ gB1 through a ones row): M = taps, N = n1, K = px
 //
-//   the wide middle layer (5x5, n1 = 128 <-> n2 = 64): train_wide.hip's
-//   conv_mfma (forward, delta1) and wgrad2 kernels (wide::op_*), on image
-//   windows past 31 x 31
+//   the wide middle layer (5x5, n1 = 128 <-> n2 = 64): the wide family's
+//   conv_mfma (forward, delta1; wconv_mfma.hpp) and wgrad2 (wgrad2.hpp)
+//   kernels through train_wide.hip's wide::op_*, on image windows past
+//   31 x 31 (the window geometry: wide_plan.hpp)
 //
 //   single output channel (n_cur == 1 / n_next == 1: layer 3, f3 x f3 x n2
 //   -> 1), per image window (forward: 21 x 21 outputs; delta2 / gW3: 64 x 64

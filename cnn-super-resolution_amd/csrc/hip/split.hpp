@@ -1,7 +1,7 @@
 // split.hpp -- fp32 products on the gfx950 bf16 matrix cores in exact-split
-// form (used by l12x6.hpp's layer 2, d1x6.hpp, forward_fused.hip and
-// train_wide.hip), and in the two-part fp16 form below (d1x6.hpp's gW1 / gB1,
-// l12x6.hpp's layer 1).
+// form (used by l12x6.hpp's layer 2, d1x6.hpp, forward_fused.hip and the wide
+// family's wl1x6.hpp, wg1x6.hpp, wl2x6.hpp and wgrad2x6.hpp), and in the
+// two-part fp16 form below (d1x6.hpp's gW1 / gB1, l12x6.hpp's layer 1).
 //
 // a = a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1)
 // (round to nearest even; every residual is exact in fp32), so

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "lds_dma.hpp"
 #include "mfma.hpp"
 #include "ops.hpp"
 #include "split.hpp"

@@ -681,7 +681,8 @@ SRCNN_API int srcnn_get_arith(void);
 /* Kernel family that served the most recent operator / network call of this
  * thread, so a slow path is never silent:
  *   "fused"   train_fused.hip / forward_fused.hip (nets with f2 == 1)
- *   "wide"    train_wide.hip (nets with a spatial middle layer)
+ *   "wide"    train_wide.hip and its kernel headers, wl1.hpp .. wgrad2x6.hpp
+ *             (nets with a spatial middle layer)
  *   "fast"    ops_fast.hip (gfx950 op-level specialisations)
  *   "generic" ops_generic.hip (any shape; one thread per output)
  *   ""        nothing launched yet on this thread */

@@ -4,7 +4,7 @@ family (srcnn_last_path) and which kernel variants, in launch order
 table, tests/golden/dispatch_table.json, is recorded on the MI355X by
 tools/record_dispatch_table.py; the comparison is exact list equality.  The
 plans that decide all of this are plan_step / plan_forward of train_fused.hip,
-train_wide.hip and forward_fused.hip."""
+wide_plan.hpp (the wide family, train_wide.hip) and forward_fused.hip."""
 import importlib.util
 import json
 import os

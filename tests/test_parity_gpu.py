@@ -353,7 +353,7 @@ def expected_train_path(name, size, path):
     past 33x33 layer 3 runs on the op-level kernels between them); the wide
     step's kernels take tiles up to 33x33 (its L2 output, 21 x 21 = 441
     pixels, fills the 14 register tiles of 32 pixels of the L2 forward;
-    train_wide.hip: plan_step(), the WidePlan); larger tiles run every conv on the windowed
+    wide_plan.hpp: plan_step(), the WidePlan); larger tiles run every conv on the windowed
     op-level gfx950 kernels ("fast"); nets outside the instantiated shapes
     (tiny: n1 = 8) on the generic ones."""
     if path == 1 or name == "tiny":
