@@ -212,6 +212,85 @@ int upscale_planes(const char* who, const void* src0, const void* src1, uint32_t
                                bits, msb != 0, semi, as_stream(stream));
 }
 
+// srcnn_resize_* (DESIGN.md 16): the output size W x H of one resampling, each
+// axis within [1x, 4x] of the source, against what the kernels of resize.hip
+// can index (as up_dims; rgb: the call writes an rgb image)
+int resize_dims(const char* who, uint32_t w, uint32_t h, uint32_t W, uint32_t H, uint32_t pad,
+                bool rgb, UpDims* d) {
+  SRCNN_REQUIRE(w > 0 && h > 0 && W > 0 && H > 0, "%s: empty image: %ux%u -> %ux%u", who, w, h, W, H);
+  SRCNN_REQUIRE(W >= w && W <= 4ull * w && H >= h && H <= 4ull * h,
+                "%s: output %ux%u is outside 1x .. 4x of the source %ux%u on an axis (upscaling only, "
+                "by at most 4)",
+                who, W, H, w, h);
+  const uint64_t lim = 0x7fffffffull, PW = (uint64_t)W + pad, PH = (uint64_t)H + pad;
+  SRCNN_REQUIRE(PW <= lim && PH <= lim && PW * PH <= lim && (!rgb || 3ull * W * H <= lim),
+                "%s: %ux%u -> %ux%u with padding %u exceeds the kernels' 32-bit index: the padded "
+                "plane's floats and the rgb bytes must each number at most 2^31-1",
+                who, w, h, W, H, pad);
+  d->W = W;
+  d->H = H;
+  d->PW = (uint32_t)PW;
+  d->PH = (uint32_t)PH;
+  return SRCNN_OK;
+}
+// one axis of srcnn_resize_planes: the source step rn / rd per output sample,
+// n source samples, N outputs
+int resize_axis(const char* who, const char* axis, uint32_t rn, uint32_t rd, uint32_t n, uint32_t N) {
+  SRCNN_REQUIRE(rn > 0, "%s: the %s ratio %u/%u has a zero numerator", who, axis, rn, rd);
+  SRCNN_REQUIRE(rd >= rn && rd <= 4ull * rn,
+                "%s: the %s ratio %u/%u is outside 1x .. 4x (den / num must lie in [1, 4])", who, axis,
+                rn, rd);
+  const uint64_t bound = ((uint64_t)n * rd + rn - 1) / rn;
+  SRCNN_REQUIRE(N <= bound, "%s: %s output size %u exceeds ceil(%u * %u / %u) = %llu", who, axis, N, n,
+                rd, rn, (unsigned long long)bound);
+  // (2 X' + 1) rn of the map, a signed 64-bit integer in the kernel
+  SRCNN_REQUIRE(2ull * N + 1 <= 0x7fffffffffffffffull / rn,
+                "%s: the %s ratio %u/%u at %u outputs exceeds the map's 64-bit integers", who, axis, rn,
+                rd, N);
+  return SRCNN_OK;
+}
+
+// The Y'CbCr operations at any output size, each behind its op-level entry
+// point and srcnn_upscale_frame_to (`who`)
+int yuv_resize_luma(const char* who, const void* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
+                    uint32_t h, uint32_t W, uint32_t H, uint32_t pad, uint32_t bits, uint32_t msb,
+                    int range, srcnn_stream_t stream) {
+  UpDims d;
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = resize_dims(who, w, h, W, H, pad, false, &d)) return rc;
+  if (int rc = plane_dims(who, w, h, pitch_y, B)) return rc;
+  if (int rc = yuv_range(who, range)) return rc;
+  SRCNN_REQUIRE(y && luma_padded, "%s: null buffer", who);
+  SRCNN_REQUIRE(!odd_address(B, y), "%s: odd address of two-byte samples", who);
+  return srcnn::yuv_resize_luma(y, pitch_y, luma_padded, w, h, W, H, pad, bits, msb != 0,
+                                range == SRCNN_YUV_FULL, as_stream(stream));
+}
+int resize_planes(const char* who, const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
+                  uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
+                  uint32_t rx_num, uint32_t rx_den, uint32_t ry_num, uint32_t ry_den, uint32_t bits,
+                  uint32_t msb, uint32_t layout, srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = yuv_layout(who, layout)) return rc;
+  const bool semi = layout == SRCNN_YUV_SEMIPLANAR;
+  if (int rc = plane_dims(who, pw, ph, src_pitch, B, semi ? 2 : 1)) return rc;
+  if (int rc = plane_dims(who, ow, oh, dst_pitch, B, semi ? 2 : 1)) return rc;
+  if (int rc = resize_axis(who, "horizontal", rx_num, rx_den, pw, ow)) return rc;
+  if (int rc = resize_axis(who, "vertical", ry_num, ry_den, ph, oh)) return rc;
+  SRCNN_REQUIRE(src0 && dst0, "%s: null buffer", who);
+  if (semi) {
+    SRCNN_REQUIRE(!src1 && !dst1, "%s: a semi-planar frame has no second chroma plane", who);
+  } else {
+    SRCNN_REQUIRE(src1 && dst1, "%s: null buffer", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, src0) && !odd_address(B, src1) && !odd_address(B, dst0) &&
+                    !odd_address(B, dst1),
+                "%s: odd address of two-byte samples", who);
+  return srcnn::resize_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, rx_num,
+                              rx_den, ry_num, ry_den, bits, msb != 0, semi, as_stream(stream));
+}
+
 // regions of the upscale workspace: padded plane | net output | reduction
 // scratch | forward workspace, each 256-byte aligned
 struct UpWs {
@@ -526,6 +605,38 @@ int srcnn_upscale_compose(const uint8_t* rgba, const float* new_luma, uint8_t* r
   return srcnn::upscale_compose(rgba, new_luma, rgb, w, h, scale, as_stream(stream));
 }
 
+int srcnn_resize_luma(const uint8_t* rgba, float* luma_padded, uint32_t w, uint32_t h, uint32_t W,
+                      uint32_t H, uint32_t pad, srcnn_stream_t stream) {
+  UpDims d;
+  if (int rc = resize_dims("resize_luma", w, h, W, H, pad, true, &d)) return rc;
+  SRCNN_REQUIRE(rgba && luma_padded, "resize_luma: null buffer");
+  return srcnn::resize_luma(rgba, luma_padded, w, h, W, H, pad, as_stream(stream));
+}
+
+int srcnn_resize_compose(const uint8_t* rgba, const float* new_luma, uint8_t* rgb, uint32_t w,
+                         uint32_t h, uint32_t W, uint32_t H, srcnn_stream_t stream) {
+  UpDims d;
+  if (int rc = resize_dims("resize_compose", w, h, W, H, 0, true, &d)) return rc;
+  SRCNN_REQUIRE(rgba && new_luma && rgb, "resize_compose: null buffer");
+  return srcnn::resize_compose(rgba, new_luma, rgb, w, h, W, H, as_stream(stream));
+}
+
+int srcnn_yuv_resize_luma(const void* y, uint32_t pitch_y, float* luma_padded, uint32_t w, uint32_t h,
+                          uint32_t W, uint32_t H, uint32_t pad, uint32_t bits, uint32_t msb, int range,
+                          srcnn_stream_t stream) {
+  return yuv_resize_luma("yuv_resize_luma", y, pitch_y, luma_padded, w, h, W, H, pad, bits, msb, range,
+                         stream);
+}
+
+int srcnn_resize_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
+                        uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow,
+                        uint32_t oh, uint32_t rx_num, uint32_t rx_den, uint32_t ry_num,
+                        uint32_t ry_den, uint32_t bits, uint32_t msb, uint32_t layout,
+                        srcnn_stream_t stream) {
+  return resize_planes("resize_planes", src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh,
+                       rx_num, rx_den, ry_num, ry_den, bits, msb, layout, stream);
+}
+
 int srcnn_yuv_upscale_luma(const uint8_t* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
                            uint32_t h, uint32_t scale, uint32_t pad, int range,
                            srcnn_stream_t stream) {
@@ -698,7 +809,7 @@ int srcnn_preload(const srcnn_net* net) {
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
       (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0 ||
       (rc = srcnn::preload_pairs()) < 0 || (rc = srcnn::preload_quality()) < 0 ||
-      (rc = srcnn::preload_yuv()) < 0)
+      (rc = srcnn::preload_yuv()) < 0 || (rc = srcnn::preload_resize()) < 0)
     return rc;
   return srcnn::preload_update();
 }
@@ -1102,6 +1213,113 @@ int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
   SRCNN_REQUIRE(fmt, "upscale_frame: null srcnn_yuv_format");
   return upscale_frame("upscale_frame", net, *fmt, src, dst, w, h, scale, params, ws, ws_bytes,
                        stream);
+}
+
+// srcnn_upscale_to / srcnn_upscale_frame_to: the net's total padding (`who`)
+static int net_pad(const char* who, const srcnn_net* net, uint32_t* pad) {
+  SRCNN_REQUIRE(net, "%s: null srcnn_net", who);
+  size_t off[6];
+  if (int rc = srcnn_net_offsets(net, off)) return rc;
+  const uint64_t pad64 = (uint64_t)net->f1 + net->f2 + net->f3 - 3;
+  SRCNN_REQUIRE(pad64 <= 0x7fffffffull, "%s: total padding %llu too large", who,
+                (unsigned long long)pad64);
+  *pad = (uint32_t)pad64;
+  return SRCNN_OK;
+}
+
+size_t srcnn_upscale_to_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t W,
+                                        uint32_t H) {
+  uint32_t pad;
+  UpDims d;
+  UpWs L;
+  if (net_pad("upscale_to", net, &pad) || resize_dims("upscale_to", w, h, W, H, pad, true, &d)) return 0;
+  return up_ws(net, d, &L) ? L.total : 0;
+}
+
+int srcnn_upscale_to(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h, uint32_t W,
+                     uint32_t H, const float* params, uint8_t* rgb, void* ws, size_t ws_bytes,
+                     srcnn_stream_t stream) {
+  uint32_t pad;
+  UpDims d;
+  if (int rc = net_pad("upscale_to", net, &pad)) return rc;
+  if (int rc = resize_dims("upscale_to", w, h, W, H, pad, true, &d)) return rc;
+  SRCNN_REQUIRE(rgba && params && rgb && ws, "upscale_to: null buffer");
+  float* out;
+  const auto luma = [&](float* plane) {
+    return srcnn_resize_luma(rgba, plane, w, h, W, H, pad, stream);
+  };
+  if (int rc = up_net("upscale_to", net, d, params, ws, ws_bytes, stream, luma, &out)) return rc;
+  return srcnn_resize_compose(rgba, out, rgb, w, h, W, H, stream);
+}
+
+// srcnn_upscale_frame_to: every check that does not need the buffers; the
+// chroma sizes of the source (cw x ch) and of the output (CW x CH)
+static int frame_to_dims(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t W, uint32_t H,
+                         uint32_t cx, uint32_t cy, YuvDims* y) {
+  const char* who = "upscale_frame_to";
+  if (int rc = net_pad(who, net, &y->pad)) return rc;
+  SRCNN_REQUIRE((cx == 2 && cy == 2) || (cx == 2 && cy == 1) || (cx == 1 && cy == 1),
+                "%s: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)", who,
+                cx, cy);
+  if (int rc = resize_dims(who, w, h, W, H, y->pad, false, &y->d)) return rc;
+  y->cw = (w - 1) / cx + 1;
+  y->ch = (h - 1) / cy + 1;
+  y->CW = (W - 1) / cx + 1;
+  y->CH = (H - 1) / cy + 1;
+  return SRCNN_OK;
+}
+
+size_t srcnn_upscale_frame_to_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                              uint32_t W, uint32_t H) {
+  YuvDims y;
+  UpWs L;
+  if (frame_to_dims(net, w, h, W, H, 1, 1, &y)) return 0;
+  return up_ws(net, y.d, &L) ? L.total : 0;
+}
+
+int srcnn_upscale_frame_to(const srcnn_net* net, const srcnn_yuv_format* fmtp,
+                           const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst, uint32_t w,
+                           uint32_t h, uint32_t W, uint32_t H, const float* params, void* ws,
+                           size_t ws_bytes, srcnn_stream_t stream) {
+  const char* who = "upscale_frame_to";
+  SRCNN_REQUIRE(fmtp, "%s: null srcnn_yuv_format", who);
+  const srcnn_yuv_format& fmt = *fmtp;
+  YuvDims y;
+  uint32_t B;
+  if (int rc = frame_to_dims(net, w, h, W, H, fmt.cx, fmt.cy, &y)) return rc;
+  if (int rc = yuv_range(who, fmt.range)) return rc;
+  if (int rc = yuv_samples(who, fmt.bits, fmt.msb, &B)) return rc;
+  if (int rc = yuv_layout(who, fmt.layout)) return rc;
+  const bool semi = fmt.layout == SRCNN_YUV_SEMIPLANAR;
+  const uint32_t nch = semi ? 2 : 1;
+  SRCNN_REQUIRE(src && dst && params && ws, "%s: null buffer", who);
+  SRCNN_REQUIRE(src->y && src->u && dst->y && dst->u, "%s: null plane", who);
+  if (semi) {
+    SRCNN_REQUIRE(!src->v && !dst->v, "%s: a semi-planar frame has no v plane", who);
+  } else {
+    SRCNN_REQUIRE(src->v && dst->v, "%s: null plane", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, src->y) && !odd_address(B, src->u) && !odd_address(B, src->v) &&
+                    !odd_address(B, dst->y) && !odd_address(B, dst->u) && !odd_address(B, dst->v),
+                "%s: odd address of two-byte samples", who);
+  // (the planes with the frames' pitches; the chroma ratio is the luma's)
+  if (int rc = plane_dims(who, w, h, src->pitch_y, B)) return rc;
+  if (int rc = plane_dims(who, W, H, dst->pitch_y, B)) return rc;
+  if (int rc = plane_dims(who, y.cw, y.ch, src->pitch_c, B, nch)) return rc;
+  if (int rc = plane_dims(who, y.CW, y.CH, dst->pitch_c, B, nch)) return rc;
+  if (int rc = resize_axis(who, "horizontal", w, W, y.cw, y.CW)) return rc;
+  if (int rc = resize_axis(who, "vertical", h, H, y.ch, y.CH)) return rc;
+  float* out;
+  const auto luma = [&](float* plane) {
+    return yuv_resize_luma(who, src->y, src->pitch_y, plane, w, h, W, H, y.pad, fmt.bits, fmt.msb,
+                           fmt.range, stream);
+  };
+  if (int rc = up_net(who, net, y.d, params, ws, ws_bytes, stream, luma, &out)) return rc;
+  if (int rc = yuv_compose_luma(who, out, dst->y, dst->pitch_y, W, H, fmt.bits, fmt.msb, fmt.range,
+                                stream))
+    return rc;
+  return resize_planes(who, src->u, src->v, src->pitch_c, y.cw, y.ch, dst->u, dst->v, dst->pitch_c,
+                       y.CW, y.CH, w, W, h, H, fmt.bits, fmt.msb, fmt.layout, stream);
 }
 
 // regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |

@@ -269,6 +269,22 @@ int upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint3
 int yuv_compose_luma(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
                      uint32_t bits, bool msb, bool full_range, hipStream_t s);
 int preload_yuv();
+// resize.hip: the same front and back end for any output size W x H with
+// w <= W <= 4w, h <= H <= 4h: the ratio of an axis is the
+// fraction w / W; resize_planes takes it explicitly (source step per output
+// sample rx_num / rx_den, ry_num / ry_den), because a frame's chroma is
+// resampled at the luma's ratio
+int resize_luma(const uint8_t* rgba, float* plane, uint32_t w, uint32_t h, uint32_t W, uint32_t H,
+                uint32_t pad, hipStream_t s);
+int resize_compose(const uint8_t* rgba, const float* nl, uint8_t* rgb, uint32_t w, uint32_t h,
+                   uint32_t W, uint32_t H, hipStream_t s);
+int yuv_resize_luma(const void* y, uint32_t pitch_y, float* plane, uint32_t w, uint32_t h, uint32_t W,
+                    uint32_t H, uint32_t pad, uint32_t bits, bool msb, bool full_range, hipStream_t s);
+int resize_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw, uint32_t ph,
+                  void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t rx_num,
+                  uint32_t rx_den, uint32_t ry_num, uint32_t ry_den, uint32_t bits, bool msb,
+                  bool semiplanar, hipStream_t s);
+int preload_resize();
 // pairs.hip: antialiased bicubic / scale (1..4) of rgba [H][W][4] into small
 // [H/scale][W/scale][4], and the cut of a grid of nx x ny tiles (tw x th,
 // origin (x0, y0), step `stride`) out of a float plane of pitch pw into

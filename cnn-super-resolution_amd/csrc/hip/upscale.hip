@@ -22,28 +22,6 @@
 namespace srcnn {
 namespace {
 
-// The two scale-1 anchors are bit-exact: the plane's interior is
-// srcnn_extract_luma's output and the composition srcnn_swap_luma's.  Under
-// -ffp-contract=fast the compiler chooses which of those kernels' products
-// fuse into an fma, and the choice shows in the last bit; luma_of (luma.hpp,
-// shared with quality.hip) and compose_px spell out the operations
-// extract_luma_kernel and swap_luma_kernel (ops_generic.hip) are built from,
-// with contraction off, so that the context they are inlined into cannot
-// change them (tests/test_upscale_gpu.py pins both against the kernels
-// themselves).
-__device__ __forceinline__ void compose_px(float r, float g, float b, float nl, uint8_t* q) {
-#pragma clang fp contract(off)
-  const float Cb = fmaf(b, 0.5f, fmaf(r, -0.1687f, g * -0.3312f));
-  const float Cr = fmaf(b, -0.0813f, fmaf(r, 0.5f, g * -0.4186f));
-  // Y = nl * 255 is never rounded on its own: Y + Cb * k is one fma
-  const float R = Cr * 1.4f + fmaf(nl, 255.0f, Cb * 0.0f);
-  const float G = fmaf(nl, 255.0f, Cb * -0.343f) - Cr * 0.711f;
-  const float B = Cr * 0.0f + fmaf(nl, 255.0f, Cb * 1.765f);
-  q[0] = (uint8_t)(unsigned)fminf(fmaxf(R, 0.0f), 255.0f);
-  q[1] = (uint8_t)(unsigned)fminf(fmaxf(G, 0.0f), 255.0f);
-  q[2] = (uint8_t)(unsigned)fminf(fmaxf(B, 0.0f), 255.0f);
-}
-
 // clamped fetch of the tile's source patch: one uchar4 load per pixel,
 // consecutive lanes consecutive pixels of a row
 template <typename T, typename Store>

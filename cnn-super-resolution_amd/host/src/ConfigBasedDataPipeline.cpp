@@ -287,6 +287,71 @@ void ConfigBasedDataPipeline::super_resolve_frame(const srcnn_yuv_format& fmt, c
         "upscale_frame");
 }
 
+size_t ConfigBasedDataPipeline::super_resolve_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w,
+                                                                 unsigned out_h) {
+  srcnn_net nt = net();
+  return srcnn_upscale_to_workspace_bytes(&nt, w, h, out_w, out_h);
+}
+
+void ConfigBasedDataPipeline::super_resolve_to(ImageData& low_res, unsigned out_w, unsigned out_h,
+                                               ImageData& result) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  require(low_res.w > 0 && low_res.h > 0, "super_resolve_to: empty image");
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_to needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  const size_t ws = srcnn_upscale_to_workspace_bytes(&nt, low_res.w, low_res.h, out_w, out_h);
+  require(ws > 0, std::string("super_resolve_to: ") + srcnn_last_error());
+  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, low_res.w, low_res.h);
+  _context->write_image(rgba, low_res, true);
+  MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, size_t(out_w) * out_h * 3);
+  void* wsp = scratch(ws);
+  if (!_upscale_to_kernel)
+    _upscale_to_kernel =
+        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_to", 0, 0, 0, false, net_defines());
+  {
+    srcnn::Context::Launch l(*_context, *_upscale_to_kernel);
+    check(srcnn_upscale_to(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), low_res.w, low_res.h, out_w, out_h,
+                           _context->fptr(_flat_params), static_cast<uint8_t*>(_context->ptr(rgb)), wsp, ws,
+                           _context->stream()),
+          "upscale_to");
+  }
+  result = ImageData(int(out_w), int(out_h), 3);
+  _context->read_buffer(rgb, 0, result.data.size(), result.data.data(), true);
+  _context->raw_memory(rgb)->release();
+  _context->raw_memory(rgba)->release();
+}
+
+size_t ConfigBasedDataPipeline::super_resolve_frame_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w,
+                                                                       unsigned out_h) {
+  srcnn_net nt = net();
+  return srcnn_upscale_frame_to_workspace_bytes(&nt, w, h, out_w, out_h);
+}
+
+void ConfigBasedDataPipeline::super_resolve_frame_to(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src,
+                                                     const srcnn_yuv_frame& dst, unsigned w, unsigned h,
+                                                     unsigned out_w, unsigned out_h, void* ws, size_t ws_bytes,
+                                                     srcnn_stream_t stream) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3),
+          "super_resolve_frame_to needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  if (stream) {
+    check(srcnn_upscale_frame_to(&nt, &fmt, &src, &dst, w, h, out_w, out_h, _context->fptr(_flat_params), ws,
+                                 ws_bytes, stream),
+          "upscale_frame_to");
+    return;
+  }
+  if (!_upscale_frame_to_kernel)
+    _upscale_frame_to_kernel =
+        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame_to", 0, 0, 0, false, net_defines());
+  srcnn::Context::Launch l(*_context, *_upscale_frame_to_kernel);
+  check(srcnn_upscale_frame_to(&nt, &fmt, &src, &dst, w, h, out_w, out_h, _context->fptr(_flat_params), ws, ws_bytes,
+                               _context->stream()),
+        "upscale_frame_to");
+}
+
 bool ConfigBasedDataPipeline::evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& q_net,
                                        QualityReport& q_bicubic) {
   check_initialized(LOAD_KERNEL_LAYERS);

@@ -132,6 +132,20 @@ class ConfigBasedDataPipeline : public DataPipeline {
                            srcnn_stream_t stream = nullptr);
   /** 0 if the net, the size or the scale is invalid (srcnn_last_error says why) */
   size_t super_resolve_yuv_workspace_bytes(unsigned w, unsigned h, unsigned scale);
+  /** super_resolve to any output size out_w x out_h within [1x, 4x] of the
+   * image's per axis: one srcnn_upscale_to call, counted as
+   * kernel 'srcnn_upscale_to'. */
+  void super_resolve_to(ImageData& low_res, unsigned out_w, unsigned out_h, ImageData& result);
+  /** 0 if the net or the sizes are invalid (srcnn_last_error says why) */
+  size_t super_resolve_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w, unsigned out_h);
+  /** super_resolve_frame to any output size out_w x out_h within [1x, 4x] of
+   * the frame's per axis: one srcnn_upscale_frame_to call (`ws`: at least
+   * super_resolve_frame_to_workspace_bytes), counted as kernel
+   * 'srcnn_upscale_frame_to' on the context's stream. */
+  void super_resolve_frame_to(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst,
+                              unsigned w, unsigned h, unsigned out_w, unsigned out_h, void* ws, size_t ws_bytes,
+                              srcnn_stream_t stream = nullptr);
+  size_t super_resolve_frame_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w, unsigned out_h);
   /** Training pairs of one full-size image, cut on the device: one
    * srcnn_make_pairs call (the image degraded by the resampling super_resolve
    * applies: down by `scale`, bicubic up again; then a grid of tile x tile
@@ -246,6 +260,8 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _forward_kernel = nullptr;
   Kernel* _upscale_kernel = nullptr;
   Kernel* _upscale_frame_kernel = nullptr;
+  Kernel* _upscale_to_kernel = nullptr;
+  Kernel* _upscale_frame_to_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
   Kernel* _planes_kernel = nullptr;
 

@@ -271,6 +271,104 @@ Event DataPipeline::yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, Memo
   return _context->mark();
 }
 
+Event DataPipeline::resize_luma(ImageData& img, MemoryHandle& raw_img, MemoryHandle& luma_padded, size_t out_w,
+                                size_t out_h, size_t padding, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(img.w > 0 && img.h > 0 && out_w >= size_t(img.w) && out_w <= 4 * size_t(img.w) &&
+              out_h >= size_t(img.h) && out_h <= 4 * size_t(img.h),
+          "resize_luma: the output size must lie within 1x .. 4x of the image's per axis");
+  _context->wait(ev);
+  size_t px = size_t(img.w) * img.h;
+  size_t plane = (out_w + padding) * (out_h + padding) * sizeof(float);
+  if (!SRCNN_HAS_SIZE(raw_img, px * 4)) raw_img = _context->create_image(srcnn::MEM_READ_WRITE, img.w, img.h);
+  _context->write_image(raw_img, img, true);
+  if (!SRCNN_HAS_SIZE(luma_padded, plane)) luma_padded = _context->allocate(srcnn::MEM_READ_WRITE, plane);
+  if (!_resize_luma_kernel) _resize_luma_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "resize_luma");
+  srcnn::Context::Launch l(*_context, *_resize_luma_kernel);
+  check(srcnn_resize_luma(static_cast<const uint8_t*>(_context->ptr(raw_img)), _context->fptr(luma_padded), img.w,
+                          img.h, uint32_t(out_w), uint32_t(out_h), uint32_t(padding), _context->stream()),
+        "resize_luma");
+  return _context->mark();
+}
+
+Event DataPipeline::resize_compose(ImageData& img, MemoryHandle org_img, MemoryHandle new_luma, MemoryHandle& target,
+                                   size_t out_w, size_t out_h, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(img.w > 0 && img.h > 0 && out_w >= size_t(img.w) && out_w <= 4 * size_t(img.w) &&
+              out_h >= size_t(img.h) && out_h <= 4 * size_t(img.h),
+          "resize_compose: the output size must lie within 1x .. 4x of the image's per axis");
+  _context->wait(ev);
+  size_t out_px = out_w * out_h;
+  if (!SRCNN_HAS_SIZE(org_img, size_t(img.w) * img.h * 4))
+    throw std::runtime_error("Invalid size of the original image buffer");
+  if (!SRCNN_HAS_SIZE(new_luma, out_px * sizeof(float)))
+    throw std::runtime_error("Invalid size of new luma buffer");
+  if (!SRCNN_HAS_SIZE(target, out_px * 3)) target = _context->allocate(srcnn::MEM_READ_WRITE, out_px * 3);
+  if (!_resize_compose_kernel)
+    _resize_compose_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "resize_compose");
+  srcnn::Context::Launch l(*_context, *_resize_compose_kernel);
+  check(srcnn_resize_compose(static_cast<const uint8_t*>(_context->ptr(org_img)), _context->fptr(new_luma),
+                             static_cast<uint8_t*>(_context->ptr(target)), img.w, img.h, uint32_t(out_w),
+                             uint32_t(out_h), _context->stream()),
+        "resize_compose");
+  return _context->mark();
+}
+
+Event DataPipeline::yuv_resize_luma(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& luma_padded,
+                                    size_t out_w, size_t out_h, size_t padding, unsigned bits, bool msb,
+                                    bool full_range, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  const size_t B = bits > 8 ? 2 : 1;
+  require(w > 0 && h > 0 && pitch_y >= w * B, "yuv_resize_luma: empty plane or pitch below the row's bytes");
+  require(out_w >= w && out_w <= 4 * w && out_h >= h && out_h <= 4 * h,
+          "yuv_resize_luma: the output size must lie within 1x .. 4x of the plane's per axis");
+  _context->wait(ev);
+  if (_context->raw_memory(y)->size < pitch_y * (h - 1) + w * B)
+    throw std::runtime_error("Invalid size of the Y plane buffer");
+  const size_t plane = (out_w + padding) * (out_h + padding) * sizeof(float);
+  if (!SRCNN_HAS_SIZE(luma_padded, plane)) luma_padded = _context->allocate(srcnn::MEM_READ_WRITE, plane);
+  if (!_yuv_resize_luma_kernel)
+    _yuv_resize_luma_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "yuv_resize_luma");
+  srcnn::Context::Launch l(*_context, *_yuv_resize_luma_kernel);
+  check(srcnn_yuv_resize_luma(_context->ptr(y), uint32_t(pitch_y), _context->fptr(luma_padded), uint32_t(w),
+                              uint32_t(h), uint32_t(out_w), uint32_t(out_h), uint32_t(padding), bits, msb ? 1 : 0,
+                              full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED, _context->stream()),
+        "yuv_resize_luma");
+  return _context->mark();
+}
+
+Event DataPipeline::resize_planes(MemoryHandle src0, MemoryHandle src1, size_t src_pitch, size_t pw, size_t ph,
+                                  MemoryHandle dst0, MemoryHandle dst1, size_t dst_pitch, size_t ow, size_t oh,
+                                  size_t rx_num, size_t rx_den, size_t ry_num, size_t ry_den, unsigned bits, bool msb,
+                                  bool semiplanar, Event* ev) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  const size_t px = (bits > 8 ? 2 : 1) * (semiplanar ? 2 : 1);  // bytes of a pixel of a plane
+  require(pw > 0 && ph > 0 && ow > 0 && oh > 0 && src_pitch >= pw * px && dst_pitch >= ow * px,
+          "resize_planes: empty plane or pitch below the row's bytes");
+  require(rx_num > 0 && ry_num > 0 && rx_den <= 0xffffffffu && ry_den <= 0xffffffffu && rx_num <= rx_den &&
+              ry_num <= ry_den,
+          "resize_planes: a ratio's numerator must be positive and at most its denominator");
+  require(semiplanar ? !src1 && !dst1 : src1 && dst1,
+          "resize_planes: two planes each way, or one each way when semi-planar");
+  _context->wait(ev);
+  for (MemoryHandle s : {src0, src1})
+    if (s && _context->raw_memory(s)->size < src_pitch * (ph - 1) + pw * px)
+      throw std::runtime_error("Invalid size of a source plane buffer");
+  for (MemoryHandle d : {dst0, dst1})
+    if (d && _context->raw_memory(d)->size < dst_pitch * (oh - 1) + ow * px)
+      throw std::runtime_error("Invalid size of a target plane buffer");
+  if (!_resize_planes_kernel)
+    _resize_planes_kernel = _context->create_kernel(srcnn::KernelKind::SwapLuma, "resize_planes");
+  srcnn::Context::Launch l(*_context, *_resize_planes_kernel);
+  check(srcnn_resize_planes(_context->ptr(src0), src1 ? _context->ptr(src1) : nullptr, uint32_t(src_pitch),
+                            uint32_t(pw), uint32_t(ph), _context->ptr(dst0), dst1 ? _context->ptr(dst1) : nullptr,
+                            uint32_t(dst_pitch), uint32_t(ow), uint32_t(oh), uint32_t(rx_num), uint32_t(rx_den),
+                            uint32_t(ry_num), uint32_t(ry_den), bits, msb ? 1 : 0,
+                            semiplanar ? SRCNN_YUV_SEMIPLANAR : SRCNN_YUV_PLANAR, _context->stream()),
+        "resize_planes");
+  return _context->mark();
+}
+
 void DataPipeline::downscale(ImageData& img, unsigned scale, ImageData& out) {
   check_initialized(LOAD_KERNEL_LUMA);
   require(scale >= 1 && scale <= 4, "downscale: scale must be 1, 2, 3 or 4");

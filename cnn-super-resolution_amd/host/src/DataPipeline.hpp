@@ -98,6 +98,28 @@ class DataPipeline {
   Event yuv_compose_luma(MemoryHandle luma, size_t w, size_t h, MemoryHandle y, size_t pitch_y, unsigned bits,
                          bool msb, bool full_range, Event* ev = nullptr);
 
+  /** Extension, any output size: upscale_luma to out_w x out_h,
+   * each within [1x, 4x] of the image's (srcnn_resize_luma). */
+  Event resize_luma(ImageData&, MemoryHandle& gpu_buf_raw_img, MemoryHandle& gpu_buf_luma_padded, size_t out_w,
+                    size_t out_h, size_t total_padding, Event* ev = nullptr);
+
+  /** Extension: upscale_compose to out_w x out_h (srcnn_resize_compose). */
+  Event resize_compose(ImageData&, MemoryHandle gpu_buf_org_img, MemoryHandle gpu_buf_new_luma,
+                       MemoryHandle& target, size_t out_w, size_t out_h, Event* ev = nullptr);
+
+  /** Extension: yuv_upscale_luma to out_w x out_h (srcnn_yuv_resize_luma). */
+  Event yuv_resize_luma(MemoryHandle y, size_t pitch_y, size_t w, size_t h, MemoryHandle& gpu_buf_luma_padded,
+                        size_t out_w, size_t out_h, size_t total_padding, unsigned bits, bool msb,
+                        bool full_range, Event* ev = nullptr);
+
+  /** Extension: upscale_planes at explicit ratios, the source step per output
+   * sample rx_num / rx_den and ry_num / ry_den (a frame's chroma takes the
+   * luma's w / W and h / H): pw x ph -> ow x oh (srcnn_resize_planes). */
+  Event resize_planes(MemoryHandle src0, MemoryHandle src1, size_t src_pitch, size_t pw, size_t ph,
+                      MemoryHandle dst0, MemoryHandle dst1, size_t dst_pitch, size_t ow, size_t oh, size_t rx_num,
+                      size_t rx_den, size_t ry_num, size_t ry_den, unsigned bits, bool msb, bool semiplanar,
+                      Event* ev = nullptr);
+
   /** Extension, the inverse of the upscale: `img` antialiased-bicubic
    * downscaled by `scale` (1..4) on the device into `out`, RGBA of
    * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
@@ -199,6 +221,10 @@ class DataPipeline {
   Kernel* _yuv_upscale_luma_kernel = nullptr;
   Kernel* _upscale_planes_kernel = nullptr;
   Kernel* _yuv_compose_luma_kernel = nullptr;
+  Kernel* _resize_luma_kernel = nullptr;
+  Kernel* _resize_compose_kernel = nullptr;
+  Kernel* _yuv_resize_luma_kernel = nullptr;
+  Kernel* _resize_planes_kernel = nullptr;
   Kernel* _downscale_kernel = nullptr;
   Kernel* _gather_tiles_kernel = nullptr;
   Kernel* _gather_batch_kernel = nullptr;

@@ -79,6 +79,40 @@ Header Header::scaled(unsigned scale) const {
   return o;
 }
 
+Header Header::resized(uint32_t W, uint32_t H) const {
+  Header o = *this;
+  o.w = W;
+  o.h = H;
+  // the picture keeps its shape: pixel aspect A * (w * H) / (W * h), reduced
+  const uint64_t up = uint64_t(w) * H, down = uint64_t(W) * h;
+  if (aspect.empty() || up == down || up == 0 || down == 0) return o;
+  const size_t colon = aspect.find(':');
+  if (colon == std::string::npos) return o;
+  uint64_t n = 0, d = 0;
+  try {
+    n = parse_dim(aspect.substr(0, colon), 'A');
+    d = parse_dim(aspect.substr(colon + 1), 'A');
+  } catch (const IOException&) {
+    return o;  // (not a fraction of integers: left as it is)
+  }
+  if (n == 0 || d == 0) return o;  // 0:0 is "unknown"
+  auto gcd = [](unsigned __int128 a, unsigned __int128 b) {
+    while (b) {
+      const unsigned __int128 t = a % b;
+      a = b;
+      b = t;
+    }
+    return a;
+  };
+  unsigned __int128 num = (unsigned __int128)n * up, den = (unsigned __int128)d * down;
+  const unsigned __int128 g = gcd(num, den);
+  num /= g;
+  den /= g;
+  if (num > 0xffffffffffffffffull || den > 0xffffffffffffffffull) return o;
+  o.aspect = std::to_string(uint64_t(num)) + ":" + std::to_string(uint64_t(den));
+  return o;
+}
+
 Header read_header(std::istream& in) {
   std::string line;
   if (!read_line(in, line, "header")) throw IOException("empty Y4M stream");

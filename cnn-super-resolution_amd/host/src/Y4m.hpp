@@ -46,6 +46,11 @@ struct Header {
   size_t frame_bytes() const { return luma_bytes() + 2 * chroma_bytes(); }
   /** the header of the stream `scale` times as large */
   Header scaled(unsigned scale) const;
+  /** the header of the stream resized to W x H: F, I, C and XCOLORRANGE as
+   * they are; A as it is when both axes have the same ratio, else the reduced
+   * fraction of A * (w * H) / (W * h), so that the picture keeps its shape
+   * (0:0, an absent token and anything that is not n:d stay as they are) */
+  Header resized(uint32_t W, uint32_t H) const;
 };
 
 /** Parse the header line off `in` (throws IOException). */

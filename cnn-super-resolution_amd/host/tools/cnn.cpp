@@ -6,7 +6,7 @@
 //       [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]
 //       [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]
 //       [--device-batches] [--augment] [--random-origins] [--frames N]
-//       [--range full|limited] [--slots N]
+//       [--range full|limited] [--slots N] [--size WxH]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -31,6 +31,12 @@
 //           frame ends the run with an error after the frames in front of it
 //           have been written.  With `profile` both slots use the pipeline's
 //           stream, so that the calls can be timed.
+//           --size WxH instead of --scale: OUT is W x H, each axis within
+//           [1x, 4x] of IN's, whatever the ratios (1280x720 -> 1920x1080,
+//           720x480 -> 1920x1080): srcnn_upscale_to for an image,
+//           srcnn_upscale_frame_to for every frame of a Y4M video, whose
+//           header then carries W, H and, where the two ratios differ, the A
+//           that keeps the picture's shape.
 // downscale: (extension) IN is a full-size image, OUT the image of 1/S the
 //           size (RGB), resampled on the device by the inverse of the upscale
 //           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
@@ -110,6 +116,8 @@ struct Args {
   bool train = false, upscale = false, downscale = false, quality = false, evaluate = false, dry = false, profile = false, help = false, version = false;
   unsigned scale = 2;      // upscale, downscale, train --from-images: --scale
   bool scale_set = false;
+  unsigned size_w = 0, size_h = 0;  // upscale: --size WxH instead of --scale
+  bool size_set = false;
   bool from_images = false;  // train --from-images: cut the pairs on the device
   size_t tile = 33, stride = 14;
   bool tile_set = false, stride_set = false;
@@ -145,7 +153,7 @@ void usage() {
          "           [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
          "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n"
          "           [--device-batches] [--augment] [--random-origins] [--frames N]\n"
-         "           [--range full|limited] [--slots N]\n\n"
+         "           [--range full|limited] [--slots N] [--size WxH]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
@@ -177,6 +185,9 @@ void usage() {
          "  --scale S             scale factor 1, 2, 3 or 4 (default 2; upscale, downscale,\n"
          "                        evaluate and train --from-images only; upscale 1: same\n"
          "                        size, every pixel through the net)\n"
+         "  --size WxH            upscale: the output size instead of --scale, each axis\n"
+         "                        within 1x .. 4x of the input's (any ratio, also a\n"
+         "                        different one per axis)\n"
          "  --frames N            upscale, Y4M: stop after N frames\n"
          "  --range full|limited  upscale, Y4M: the luma range (default: the header's\n"
          "                        XCOLORRANGE, else limited)\n"
@@ -285,6 +296,18 @@ bool parse(int argc, char** argv, Args& a) {
       a.scale = unsigned(v[0] - '0');
       a.scale_set = true;
     }
+    else if (s == "--size") {
+      const std::string v = value("--size");
+      const size_t x = v.find('x');
+      auto number = [](const std::string& t) -> unsigned {
+        if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return 0;
+        return unsigned(std::stoul(t));
+      };
+      a.size_w = x == std::string::npos ? 0 : number(v.substr(0, x));
+      a.size_h = x == std::string::npos ? 0 : number(v.substr(x + 1));
+      if (a.size_w == 0 || a.size_h == 0) throw std::runtime_error("--size must be WxH, two positive integers");
+      a.size_set = true;
+    }
     else if (s == "dry") a.dry = true;
     else if (s == "profile") a.profile = true;
     else if (s == "-c" || s == "--config") a.config = value("--config");
@@ -317,6 +340,8 @@ bool parse(int argc, char** argv, Args& a) {
   if (a.scale_set && !a.upscale && !a.downscale && !a.evaluate && !a.from_images)
     throw std::runtime_error(
         "--scale needs the upscale mode, the downscale mode, the evaluate mode or train --from-images");
+  if (a.size_set && a.scale_set) throw std::runtime_error("--size and --scale exclude each other");
+  if (a.size_set && !a.upscale) throw std::runtime_error("--size needs the upscale mode");
   if ((a.frames_set || a.range >= 0 || a.slots_set) && !a.upscale)
     throw std::runtime_error("--frames, --range and --slots need the upscale mode");
   if (!a.ref.empty() && !a.quality) throw std::runtime_error("--ref needs the quality mode");
@@ -389,6 +414,28 @@ int forward(ConfigBasedDataPipeline& p, const Args& a) {
   return 0;
 }
 
+/** --size against the input's size, read from the file's header or image on
+ * the host, before any device is opened: each axis within [1x, 4x] */
+void check_size(const Args& a) {
+  uint64_t w, h;
+  std::ifstream in(a.in, std::ios::binary);
+  char magic[9] = {};
+  if (in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0) {
+    in.seekg(0);
+    const srcnn::y4m::Header hd = srcnn::y4m::read_header(in);
+    w = hd.w, h = hd.h;
+  } else {
+    ImageData img;
+    srcnn::image::load(a.in, img, 4);
+    w = uint64_t(img.w), h = uint64_t(img.h);
+  }
+  if (a.size_w >= w && a.size_w <= 4 * w && a.size_h >= h && a.size_h <= 4 * h) return;
+  throw std::runtime_error("--size " + std::to_string(a.size_w) + "x" + std::to_string(a.size_h) +
+                           " is outside 1x .. 4x of the input's " + std::to_string(w) + "x" + std::to_string(h) +
+                           " per axis: the width must lie in " + std::to_string(w) + " .. " + std::to_string(4 * w) +
+                           ", the height in " + std::to_string(h) + " .. " + std::to_string(4 * h));
+}
+
 /** One frame in flight of `cnn upscale` on a Y4M stream: its own stream,
  * pinned host buffers, device frames and workspace.  Everything is released
  * when the slot goes, whatever ended the run. */
@@ -428,7 +475,8 @@ struct FrameSlot {
   }
 };
 
-/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_frame.  Any
+/** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_frame
+ * (--scale) or srcnn_upscale_frame_to (--size).  Any
  * failed call throws, which ends the run before another frame is started. */
 int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   namespace y4m = srcnn::y4m;
@@ -437,12 +485,13 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
     hd.full_range = a.range == 1;
     hd.has_range = true;
   }
-  const y4m::Header ohd = hd.scaled(a.scale);
+  const y4m::Header ohd = a.size_set ? hd.resized(a.size_w, a.size_h) : hd.scaled(a.scale);
   // a deep stream holds its values in the low bits of two-byte words, in planes
   const srcnn_yuv_format fmt{hd.bits, 0, SRCNN_YUV_PLANAR, hd.cx, hd.cy, hd.full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED};
   std::cout << "Y4M video: " << hd.w << "x" << hd.h << " C" << hd.chroma << ", "
             << (hd.full_range ? "full" : "limited") << " range -> " << ohd.w << "x" << ohd.h << std::endl;
-  const size_t ws_bytes = p.super_resolve_yuv_workspace_bytes(hd.w, hd.h, a.scale);
+  const size_t ws_bytes = a.size_set ? p.super_resolve_frame_to_workspace_bytes(hd.w, hd.h, ohd.w, ohd.h)
+                                     : p.super_resolve_yuv_workspace_bytes(hd.w, hd.h, a.scale);
   srcnn::require(ws_bytes > 0, std::string("upscale: ") + srcnn_last_error());
   std::ofstream out;
   const bool store = !a.dry && !a.out.empty();
@@ -479,7 +528,11 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
       break;
     }
     srcnn::check(srcnn_memcpy_h2d(s.dev_in, s.host_in, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
-    p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
+    if (a.size_set)
+      p.super_resolve_frame_to(fmt, s.src, s.dst, hd.w, hd.h, ohd.w, ohd.h, s.ws, ws_bytes,
+                               own_streams ? s.stream : nullptr);
+    else
+      p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
     s.busy = true;
   }
   for (unsigned i = 0; i < a.slots; ++i) drain(slots[(k + i) % a.slots]);  // the oldest first
@@ -494,8 +547,9 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   return rc;
 }
 
-/** `cnn upscale`: the low-resolution image through srcnn_upscale, or a Y4M
- * video through srcnn_upscale_frame frame by frame */
+/** `cnn upscale`: the low-resolution image through srcnn_upscale (--size:
+ * srcnn_upscale_to), or a Y4M video through srcnn_upscale_frame (--size:
+ * srcnn_upscale_frame_to) frame by frame */
 int upscale(ConfigBasedDataPipeline& p, const Args& a) {
   {
     std::ifstream in(a.in, std::ios::binary);
@@ -509,7 +563,8 @@ int upscale(ConfigBasedDataPipeline& p, const Args& a) {
     throw std::runtime_error("--frames, --range and --slots need a Y4M input");
   ImageData img, res;
   srcnn::image::load(a.in, img, 4);
-  p.super_resolve(img, a.scale, res);
+  if (a.size_set) p.super_resolve_to(img, a.size_w, a.size_h, res);
+  else p.super_resolve(img, a.scale, res);
   if (!a.dry && !a.out.empty()) {
     std::cout << "Saving result image to: '" << a.out << "'" << std::endl;
     srcnn::image::write(a.out.c_str(), res);
@@ -1031,6 +1086,10 @@ int main(int argc, char** argv) {
     std::cout << "Evaluate mode, scale: " << a.scale << ", shave: " << a.shave << std::endl
               << "Full-size image or directory: " << a.in << std::endl
               << "Report: " << (a.dry || a.out.empty() ? "-" : a.out) << std::endl;
+  else if (a.upscale && a.size_set)
+    std::cout << "Upscale mode, size: " << a.size_w << "x" << a.size_h << std::endl
+              << "Input image: " << a.in << std::endl
+              << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   else if (a.upscale)
     std::cout << "Upscale mode, scale: " << a.scale << std::endl
               << "Input image: " << a.in << std::endl
@@ -1040,6 +1099,7 @@ int main(int argc, char** argv) {
               << "Input image: " << a.in << std::endl
               << "Output: " << (a.dry ? "-" : a.out) << std::endl;
   try {
+    if (a.size_set) check_size(a);
     if (a.downscale) {
       srcnn::Context context;
       context.init(a.profile, a.device);

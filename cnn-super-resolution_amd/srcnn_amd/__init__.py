@@ -115,6 +115,10 @@ SIGNATURES = {
     "srcnn_yuv_upscale_luma16": (_I, [_P, _U, _P, _U, _U, _U, _U, _U, _U, _I, _P]),
     "srcnn_yuv_compose_luma16": (_I, [_P, _P, _U, _U, _U, _U, _U, _I, _P]),
     "srcnn_upscale_planes": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _U, _U, _U, _P]),
+    "srcnn_resize_luma": (_I, [_P, _P, _U, _U, _U, _U, _U, _P]),
+    "srcnn_resize_compose": (_I, [_P, _P, _P, _U, _U, _U, _U, _P]),
+    "srcnn_yuv_resize_luma": (_I, [_P, _U, _P, _U, _U, _U, _U, _U, _U, _U, _I, _P]),
+    "srcnn_resize_planes": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _U, _P]),
     "srcnn_downscale_rgba": (_I, [_P, _P, _U, _U, _U, _P]),
     "srcnn_gather_tiles": (_I, [_P, _U, _U, _U, _U, _U, _U, _U, _U, _U, _I, _P, _P, _P]),
     "srcnn_gather_batch": (_I, [_P, _U, _P, _U, _U, _U, _P, _P, _P, _P]),
@@ -128,6 +132,10 @@ SIGNATURES = {
     "srcnn_upscale_yuv_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale_yuv": (_I, [_NP, _FP, _FP, _U, _U, _U, _U, _U, _I, _P, _P, _S, _P]),
     "srcnn_upscale_frame": (_I, [_NP, _MP, _FP, _FP, _U, _U, _U, _P, _P, _S, _P]),
+    "srcnn_upscale_to_workspace_bytes": (_S, [_NP, _U, _U, _U, _U]),
+    "srcnn_upscale_to": (_I, [_NP, _P, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
+    "srcnn_upscale_frame_to_workspace_bytes": (_S, [_NP, _U, _U, _U, _U]),
+    "srcnn_upscale_frame_to": (_I, [_NP, _MP, _FP, _FP, _U, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_evaluate_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_evaluate": (_I, [_NP, _P, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_net_offsets": (_I, [_NP, ctypes.POINTER(_S)]),
@@ -425,6 +433,34 @@ def upscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh,
           scale, bits, msb, layout, s)
 
 
+def resize_luma(rgba, luma_padded, w, h, W, H, pad, s=None):
+    """upscale_luma to any output size W x H, w <= W <= 4w and h <= H <= 4h:
+    the padded plane [(H+pad)][(W+pad)] f32 (srcnn_resize_luma)."""
+    _call("srcnn_resize_luma", ptr(rgba), ptr(luma_padded), w, h, W, H, pad, s)
+
+
+def resize_compose(rgba, new_luma, rgb, w, h, W, H, s=None):
+    """upscale_compose to any output size: rgba [h][w][4] u8 + new_luma [H][W]
+    f32 -> rgb [H][W][3] u8 (srcnn_resize_compose)."""
+    _call("srcnn_resize_compose", ptr(rgba), ptr(new_luma), ptr(rgb), w, h, W, H, s)
+
+
+def yuv_resize_luma(y, pitch_y, luma_padded, w, h, W, H, pad, bits, msb, yuv_range, s=None):
+    """yuv_upscale_luma16 to any output size: Y [h][w] of `bits` bits ->
+    the padded plane [(H+pad)][(W+pad)] f32 (srcnn_yuv_resize_luma)."""
+    _call("srcnn_yuv_resize_luma", ptr(y), pitch_y, ptr(luma_padded), w, h, W, H, pad, bits, msb, yuv_range, s)
+
+
+def resize_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, rx_num, rx_den, ry_num, ry_den,
+                  bits, msb, layout, s=None):
+    """upscale_planes at the explicit ratios rx_num / rx_den and ry_num / ry_den
+    (the source step per output sample; a frame's chroma takes the luma's w / W
+    and h / H): [ph][pw] -> [oh][ow], ow <= ceil(pw * rx_den / rx_num), rows
+    likewise (srcnn_resize_planes)."""
+    _call("srcnn_resize_planes", ptr(src0), ptr(src1), src_pitch, pw, ph, ptr(dst0), ptr(dst1), dst_pitch, ow, oh,
+          rx_num, rx_den, ry_num, ry_den, bits, msb, layout, s)
+
+
 def downscale_rgba(rgba, small, W, H, scale, s=None):
     """rgba [H][W][4] u8 -> antialiased bicubic / scale, small
     [H//scale][W//scale][4] u8, alpha 255 (srcnn_downscale_rgba)."""
@@ -641,6 +677,29 @@ def upscale_frame(net, fmt, src, dst, w, h, scale, params, ws, ws_bytes, s=None)
     the workspace is upscale_yuv_workspace_bytes (srcnn_upscale_frame)."""
     _call("srcnn_upscale_frame", ctypes.byref(net), ctypes.byref(fmt) if fmt is not None else None,
           ctypes.byref(src), ctypes.byref(dst), w, h, scale, ptr(params), ptr(ws), ws_bytes, s)
+
+
+def upscale_to_workspace_bytes(net, w, h, W, H):
+    return _lib.srcnn_upscale_to_workspace_bytes(ctypes.byref(net), w, h, W, H)
+
+
+def upscale_to(net, rgba, w, h, W, H, params, rgb, ws, ws_bytes, s=None):
+    """upscale to any output size W x H within [1x, 4x] of w x h per axis
+    (srcnn_upscale_to): resize_luma, sub_mean over the padded plane, forward,
+    resize_compose."""
+    _call("srcnn_upscale_to", ctypes.byref(net), ptr(rgba), w, h, W, H, ptr(params), ptr(rgb), ptr(ws), ws_bytes, s)
+
+
+def upscale_frame_to_workspace_bytes(net, w, h, W, H):
+    return _lib.srcnn_upscale_frame_to_workspace_bytes(ctypes.byref(net), w, h, W, H)
+
+
+def upscale_frame_to(net, fmt, src, dst, w, h, W, H, params, ws, ws_bytes, s=None):
+    """upscale_frame to any output size W x H within [1x, 4x] of w x h per axis
+    (srcnn_upscale_frame_to): yuv_resize_luma, sub_mean, forward,
+    yuv_compose_luma16, and resize_planes at the luma's ratios for the chroma."""
+    _call("srcnn_upscale_frame_to", ctypes.byref(net), ctypes.byref(fmt) if fmt is not None else None,
+          ctypes.byref(src), ctypes.byref(dst), w, h, W, H, ptr(params), ptr(ws), ws_bytes, s)
 
 
 def evaluate_workspace_bytes(net, W, H, scale):

@@ -289,6 +289,50 @@ SRCNN_API int srcnn_upscale_planes(const void* src0, const void* src1, uint32_t 
                                    uint32_t bits, uint32_t msb, uint32_t layout,
                                    srcnn_stream_t stream);
 
+/* The same front and back end for any output size (DESIGN.md 16 is the spec):
+ * the source is w x h, the output W x H with w <= W <= 4w and h <= H <= 4h,
+ * each axis on its own (only upscaling, so nothing is antialiased).  The
+ * resampling is the one above with the ratio as a fraction: the source step
+ * per output sample is rn / rd (w / W, h / H); for output index X',
+ * n = (2X'+1) rn - rd, D = 2 rd, b = floor(n / D), t = (n - b D) / D, taps
+ * b-1 .. b+2 clamped to the source, the Keys weights at t+1, t, 1-t, 2-t
+ * computed in double and rounded once to fp32.  Margins, luma, composition,
+ * rounding, sample formats, pitches and ranges are those of the calls above.
+ * At an integer ratio the results meet the same bounds as the scale calls'
+ * but need not equal them bit for bit.
+ *
+ * srcnn_resize_luma: rgba [h][w][4] u8 -> luma_padded [(H+pad)][(W+pad)] f32.
+ * With W = w and H = h the interior is srcnn_extract_luma's output bit for bit.
+ * srcnn_resize_compose: rgba + new_luma [H][W] -> rgb [H][W][3] u8.  With
+ * W = w and H = h it is srcnn_swap_luma(w, h, w, h) byte for byte.
+ * srcnn_yuv_resize_luma: Y [h][w] of `bits` bits -> luma_padded; with W = w,
+ * H = h and full range the interior is float(Y) / float(2^bits - 1).
+ * srcnn_resize_planes: src0, src1 [ph][pw] -> dst0, dst1 [oh][ow] (or (U, V)
+ * pairs in src0 / dst0, as srcnn_upscale_planes) at the explicit ratios
+ * rx_num / rx_den and ry_num / ry_den; ow <= ceil(pw * rx_den / rx_num) and
+ * oh <= ceil(ph * ry_den / ry_num).  A frame's chroma is resampled at the
+ * luma's ratios w / W and h / H, not at CW / cw: DESIGN.md 14.1's crop rule,
+ * generalised.  At ratios 1/1 the output is the source sample for sample.
+ *
+ * SRCNN_ERR_INVALID, before any launch: a zero size; W < w, W > 4w, H < h or
+ * H > 4h; a ratio whose den / num lies outside [1, 4] or a zero numerator; ow
+ * or oh beyond its bound; whatever the scale calls reject for pitches, bits,
+ * msb, layout, range and null pointers; more than 2^31-1 plane floats, rgb
+ * bytes or samples in a plane. */
+SRCNN_API int srcnn_resize_luma(const uint8_t* rgba, float* luma_padded, uint32_t w, uint32_t h,
+                                uint32_t W, uint32_t H, uint32_t pad, srcnn_stream_t stream);
+SRCNN_API int srcnn_resize_compose(const uint8_t* rgba, const float* new_luma, uint8_t* rgb,
+                                   uint32_t w, uint32_t h, uint32_t W, uint32_t H,
+                                   srcnn_stream_t stream);
+SRCNN_API int srcnn_yuv_resize_luma(const void* y, uint32_t pitch_y, float* luma_padded, uint32_t w,
+                                    uint32_t h, uint32_t W, uint32_t H, uint32_t pad, uint32_t bits,
+                                    uint32_t msb, int range, srcnn_stream_t stream);
+SRCNN_API int srcnn_resize_planes(const void* src0, const void* src1, uint32_t src_pitch,
+                                  uint32_t pw, uint32_t ph, void* dst0, void* dst1,
+                                  uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t rx_num,
+                                  uint32_t rx_den, uint32_t ry_num, uint32_t ry_den, uint32_t bits,
+                                  uint32_t msb, uint32_t layout, srcnn_stream_t stream);
+
 /* Training pairs from a full-size image, on the device (an MI355X extension;
  * the reference's pairs are made on the host, one file per sample).  The
  * training-side mirror of the upscaling front end: DESIGN.md 11.1 is the spec.
@@ -458,8 +502,8 @@ typedef struct srcnn_net {
 
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
  * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale,
- * srcnn_upscale_yuv) launch for this net, and the kernels of srcnn_make_pairs
- * and srcnn_quality.
+ * srcnn_upscale_yuv, srcnn_upscale_to, srcnn_upscale_frame_to) launch for this
+ * net, and the kernels of srcnn_make_pairs and srcnn_quality.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -605,6 +649,38 @@ SRCNN_API int srcnn_upscale_frame(const srcnn_net* net, const srcnn_yuv_format* 
                                   const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst,
                                   uint32_t w, uint32_t h, uint32_t scale, const float* params,
                                   void* ws, size_t ws_bytes, srcnn_stream_t stream);
+
+/* srcnn_upscale and srcnn_upscale_frame to any output size W x H within
+ * [1x, 4x] of the source per axis.  srcnn_upscale_to is
+ *   srcnn_resize_luma (pad = f1+f2+f3-3) -> srcnn_sub_mean -> srcnn_forward ->
+ *   srcnn_resize_compose
+ * and srcnn_upscale_frame_to is
+ *   srcnn_yuv_resize_luma(src->y, pad = f1+f2+f3-3) -> plane
+ *   srcnn_sub_mean, srcnn_forward as in srcnn_upscale_yuv
+ *   srcnn_yuv_compose_luma16(out -> dst->y)
+ *   srcnn_resize_planes(src->u, src->v -> dst->u, dst->v) at the ratios w / W
+ *     and h / H, the chroma planes [ceil(h/cy)][ceil(w/cx)] ->
+ *     [ceil(H/cy)][ceil(W/cx)]
+ * each byte-identical to its calls, for every net srcnn_forward accepts;
+ * stream-ordered, no host synchronisation, no allocation.  `ws` holds the
+ * plane, the net output, the reduction scratch and the forward workspace (each
+ * 256-byte aligned) under the memory contract at srcnn_train_workspace_bytes;
+ * of dst only the samples of each row are written, nothing between the rows.
+ * The workspace queries return 0 where the call would be invalid.  Errors as
+ * the op-level calls and as srcnn_upscale / srcnn_upscale_frame, before any
+ * launch; SRCNN_ERR_WORKSPACE for a workspace that is too small. */
+SRCNN_API size_t srcnn_upscale_to_workspace_bytes(const srcnn_net* net, uint32_t w, uint32_t h,
+                                                  uint32_t W, uint32_t H);
+SRCNN_API int srcnn_upscale_to(const srcnn_net* net, const uint8_t* rgba, uint32_t w, uint32_t h,
+                               uint32_t W, uint32_t H, const float* params, uint8_t* rgb, void* ws,
+                               size_t ws_bytes, srcnn_stream_t stream);
+SRCNN_API size_t srcnn_upscale_frame_to_workspace_bytes(const srcnn_net* net, uint32_t w,
+                                                        uint32_t h, uint32_t W, uint32_t H);
+SRCNN_API int srcnn_upscale_frame_to(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                                     const srcnn_yuv_frame* src, const srcnn_yuv_frame* dst,
+                                     uint32_t w, uint32_t h, uint32_t W, uint32_t H,
+                                     const float* params, void* ws, size_t ws_bytes,
+                                     srcnn_stream_t stream);
 
 /* "How many dB over bicubic?" in one call: the full-size ground truth rgba
  * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at
