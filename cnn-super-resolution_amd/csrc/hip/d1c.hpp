@@ -1,6 +1,8 @@
 // d1c.hpp -- kernel 3 of the fused step (delta1 + gW2/gB2 + gW1/gB1) in the
 // cooperative-chunk form, for the reference default net (n1 = 64, n2 = 32).
-// Included by train_fused.hip inside namespace srcnn::fused.
+// Included by train_fused.hip inside namespace srcnn::fused, after
+// fused_layout.hpp (Geom, the kD1c* sizes and d1c_lds_bytes, the LDS bytes of
+// the regions carved below); uses train_fused.hip's g_clk.
 //
 // Same mathematics as d1_grad12_kernel (layer_deltas.cl:42-127 with f = 1,
 // backpropagate.cl:56-114 for layers 1 and 2), different work split: the four
@@ -42,21 +44,7 @@ using lds_dma::dma16;
 using lds_dma::dma16s;
 using lds_dma::dma4s;
 
-// 4-wave teams per block, on alternate chunks of a sample (two teams per
-// block, 512 slabs instead of 1024: d1 0.4065 vs 0.399 ms)
-constexpr int kD1cTeams = 1;
-constexpr int kD1cOcc = 4;                           // waves per SIMD (launch bound: 128 VGPRs)
-constexpr int kD1cGrid = 256 * kD1cOcc / kD1cTeams;  // all blocks resident
-constexpr int kD1cS = 40;       // X tile row stride in LDS (8 mod 32)
-constexpr int kD1cMaxPx = 1024; // pixel slots of the X offset table (nch * 32)
-
 __device__ float g_d1c_zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // 16-B zero source (delta2 rows past the sample)
-
-inline bool d1c_fits(int w, int h) { return w <= kD1cS && ((w - 8) * (h - 8) + 31) / 32 * 32 <= kD1cMaxPx; }
-inline int d1c_xs_floats(int h) { return (kD1cS * h + 63) / 64 * 64; }
-inline size_t d1c_lds_bytes(int w, int h) {
-  return (size_t)(kD1cTeams * 6144 + 2 * d1c_xs_floats(h) + ((w - 8) * (h - 8) + 31) / 32 * 32) * sizeof(float);
-}
 
 template <int F1>
 __global__ __launch_bounds__(256 * kD1cTeams, kD1cOcc) void d1c_grad12_kernel(const float* __restrict__ X,

@@ -1,7 +1,10 @@
 // d1x6.hpp -- kernel 3 of the fused step (delta1 + gW1/gB1 + gW2/gB2) for
 // the reference default net (n1 = 64, n2 = 32, f1 = 9) in split-bf16
 // products (split.hpp), paired with l12x6 (its A1 layout and pixel order,
-// runs.hpp).  Included by train_fused.hip inside namespace srcnn::fused.
+// runs.hpp).  Included by train_fused.hip inside namespace srcnn::fused, after
+// d3taps.hpp, fused_layout.hpp (its LDS layout D6Lds, Geom, RunGeom, D3Geom,
+// d6tr.hpp's address maps) and l12x6.hpp (the mfma:: names it imports); uses
+// train_fused.hip's g_clk.
 // Same mathematics as d1c_grad12_kernel (layer_deltas.cl:42-127 with f = 1,
 // backpropagate.cl:56-114 for layers 1 and 2).
 //
@@ -40,10 +43,6 @@
 // 30 MB written and read back per step.)
 // One wave per SIMD (512 registers: 128 accumulators + operands).
 
-constexpr int kD6W2 = 2 * 2 * 3 * 512;  // delta1's W2 image, bf16: [t][k][part][lane][8]
-constexpr int kD6W3 = 2 * 3 * 512;      // delta2's W3 image (kD3), bf16: [s][part][lane][8]
-constexpr int kD6Sc = 32 * 36;           // per-wave delta2 transpose scratch (floats)
-
 // kD3: the waves' per-sample maxima in the constant region (dword offsets)
 constexpr int kD6Mxx = 12, kD6Mx3 = 25;
 // kD3: gW1's accumulators hold 2^EW x the sum (the bias column 2^EB x); a
@@ -54,86 +53,6 @@ constexpr int kD6ExWin = 6, kD6ExMid = 3;
 // no sample's scale lies more than 2^kD6Grow above the largest sample's seen
 // (the accumulators cannot overflow: 2^30 per product, < 2^20 slots per wave)
 constexpr int kD6Grow = 70;
-
-// layer-3 geometry for the kD3 form (delta2 formed here from delta3)
-struct D3Geom {
-  int w3, h3, f3;
-};
-
-struct D6Lds {
-  int st;      // T image column stride (dwords per column, >= 4 cr + 9)
-  int tcols;   // T image columns (the column runs' x range + 8)
-  int rs;      // R image row stride (pixels): the least >= w with rs = 9 (mod 64)
-  int rdw;     // R image dwords (3 parts interleaved)
-  int tdw;     // T image dwords
-  int xbuf;    // one X buffer (dwords): R then T
-  // kD3: the delta3 pair image, rows of three part rows side by side: gw
-  // columns per part, row stride gs (dwords), gh rows; one buffer d3buf dwords
-  int gw, gs, gh, d3buf;
-  int w2, xb, sc, slots, runs, cst, w3i, d3tab, d3img, bytes;  // byte offsets
-  int tr;  // kD3: 1 = delta2 part images in the sc region (d6tr.hpp), 0 = the fp32 transpose scratch
-  __host__ __device__ D6Lds(int w, int h, const RunGeom& rg, bool d3 = false) {
-    st = 4 * rg.cr + 9;
-    if (st < h + 1) st = h + 1;
-    tcols = rg.b ? rg.b + 8 : 0;
-    // a tap (dy, dx) of gW1's X operand sits 3 (dy rs + dx) dwords past its
-    // run base, = 3 (9 dy + dx) = 3 tap (mod 64) for rs = 9 (mod 64): the 32
-    // taps of a half-wave hit 32 distinct banks (at rs = w = 33 two taps
-    // shared a bank: 53% of d1x6's LDS-active cycles were bank conflicts)
-    rs = w + ((9 - w) % 64 + 64) % 64;
-    rdw = 3 * (rs * h + 1);
-    tdw = 3 * tcols * st;
-    xbuf = rdw + tdw;
-    w2 = 0;
-    xb = kD6W2 * 2;
-    sc = xb + 2 * xbuf * 4;
-    sc = (sc + 15) & ~15;
-    gw = gs = gh = d3buf = 0;
-    // slot (py, px) reads delta3 at image row py + 5 - dy, column px + 7 - dx
-    // (pairs of columns, d3taps.hpp); the padded row stride puts a chunk's 32
-    // slots at one fixed offset on 32 banks (as l12x6's X image).
-    // kD3 takes, in this order: the waves' delta2 part images (d6tr.hpp, tr)
-    // with padded delta3 rows; the fp32 transpose scratch (1.5 KB less per
-    // wave) with padded rows; the images with unpadded rows; the scratch with
-    // unpadded rows.  The scratch forms are the layouts this kernel had before
-    // the images, and padded rows come before the images: every shape fits
-    // exactly where it did, and none loses the padded rows it had
-    // (33x33: 151.8 KB with images and padded rows; unpadded rows' reads were
-    // 11 of d1x6's 25 conflict points)
-    const int ntry = d3 ? 4 : 1;
-    for (int k = 0; k < ntry; k++) {
-      tr = d3 && !(k & 1);
-      const bool pad = k < 2;
-      slots = sc + (tr ? d6tr_wave_off(4) : 4 * kD6Sc * 4);
-      runs = slots + rg.nch * 32 * 4;
-      cst = runs + rg.nch * 8 * 4;
-      bytes = cst + 32 * 4;
-      w3i = d3tab = d3img = bytes;
-      if (!d3) break;
-      gw = rg.ow + 8;
-      gh = rg.oh + 5;
-      const int a4 = (4 * rg.a) % 32;
-      gs = pad ? 3 * gw + ((a4 - 3 * gw) % 32 + 32) % 32 : 3 * gw;
-      d3buf = gh * gs;
-      w3i = (cst + 32 * 4 + 15) & ~15;
-      // (with the part images the slot's delta3 offset shares the slot
-      // table's dword, d6_slot_pack: a table of its own is 2.5 KB at 33x33,
-      // which the images need)
-      d3tab = tr ? slots : w3i + kD6W3 * 2;
-      d3img = tr ? w3i + kD6W3 * 2 : d3tab + rg.nch * 32 * 4;
-      bytes = d3img + 3 * d3buf * 4 + 16;  // (+ the zeroing's last 16-B store)
-      if (bytes <= 160 * 1024) break;
-    }
-    // the final reduction's scratch and the slab staging after it
-    const int red_bytes = 4 * 4 * 16 * 64 * 4 + (81 * 64 + 64 + 64 * 32 + 32) * 4;
-    if (bytes < red_bytes) bytes = red_bytes;
-  }
-};
-
-inline bool d1x6_fits(int w, int h, bool d3 = false) {
-  const RunGeom rg = run_geom(w - 8, h - 8);
-  return w <= 57 && D6Lds(w, h, rg, d3).bytes <= 160 * 1024 && (!d3 || rg.nch >= 4);
-}
 
 // the all-zero delta2 row that dummy slots load (runs.hpp: slots past the
 // tile), with the lane-half offset and the four 16-B quads of a real row

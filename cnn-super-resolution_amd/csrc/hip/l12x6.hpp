@@ -1,7 +1,9 @@
 // l12x6.hpp -- kernel 1 of the fused step (L1 + L2 forward) for the reference
 // default net (n1 = 64, n2 = 32, f1 = 9) with its products on the matrix cores
 // in exact-split form.  Included by train_fused.hip inside namespace
-// srcnn::fused; same outputs (blocked A1, A2 rows) and the same mathematics as
+// srcnn::fused, after fused_layout.hpp (its LDS layout H6Lds, the rule X6Lds
+// by which a tile takes it, Geom, RunGeom, kL12Regs); uses train_fused.hip's
+// g_clk and ops.hpp's LazyUpdate.  Same outputs (blocked A1, A2 rows) and the same mathematics as
 // l12_fwd_kernel (layer_uber_kernel.cl:36-96 for layers 1 and 2).
 //
 // Split products (split.hpp).  Layer 2 is in the bf16 form ("x6"): every fp32
@@ -53,73 +55,6 @@ using mfma::split8;
 using mfma::split8_h;
 using mfma::split8_pk;
 using mfma::u32x4;
-
-constexpr int kX6KS = 5;                  // 16-slot k-steps of layer 1
-constexpr int kX6W1 = kX6KS * 2 * 3 * 512;  // W1 image in three bf16 parts (X6Lds's rule only)
-constexpr int kX6W2 = 4 * 3 * 512;          // W2 image, bf16: [m][part][lane][8]
-
-// per wave: the A2 regroup scratch [32 slots][32 channels] (16-B quads
-// XOR-swizzled by slot: quad c of slot p at quad c ^ (p & 7)) and the
-// slots' pixels
-constexpr int kX6Sc = 32 * 32 + 32;
-// The X pair image holds, per image row, the part rows side by side
-// (dword y rs + w q + x = the part-q pair (x_{y,x}, x_{y,x+1})).  A
-// half-wave's L1 B-operand read covers the 32 slots of a chunk: 8 row runs
-// of 4 pixels, a row's ow / 4 runs then the next row's, so with rs3 = 4 (ow /
-// 4) (mod 32) its 32 dwords are consecutive modulo 32 -- 32 distinct banks
-// (ds_read_b32 banks (a / 4) mod 32 per half-wave).  At the unpadded stride
-// (the round-5 part-major layout had rows of w dwords) two rows of a chunk
-// shared banks: every such read was 2-way.  The padded stride where it fits
-// in the 80 KB of two blocks per CU, else 3 w.  xs: the fp32 tile (tap (8, 8)
-// and k-step 4), row stride w.
-// X6Lds is that layout on the three-part (bf16) sizes the kernel had through
-// round 11: kept as the rule by which a tile takes l12x6 (l12x6_fits) and the
-// padded stride, so the dispatch stays what it was.
-struct X6Lds {
-  int rs3, r, xs, a2sc, bytes;  // pair-image row stride (dwords); byte offsets
-  bool pad;                     // the padded stride fits
-  __host__ __device__ X6Lds(int w, int h) {
-    const int base = (kX6W1 + kX6W2) * 2 + (128 + 32) * 4;
-    const int a4 = (4 * ((w - 8) / 4)) % 32;
-    r = base;
-    rs3 = 3 * w + ((a4 - 3 * w) % 32 + 32) % 32;
-    pad = true;
-    for (int k = 0; k < 2; k++) {
-      xs = r + (rs3 * h + 1) * 4;
-      a2sc = (xs + w * h * 4 + 15) & ~15;
-      bytes = a2sc + 4 * kX6Sc * 4;
-      if (bytes <= 80 * 1024) break;
-      rs3 = 3 * w;
-      pad = false;
-    }
-  }
-};
-
-inline bool l12x6_fits(int w, int h) {
-  return w * h <= kXsMax && X6Lds(w, h).bytes <= 80 * 1024;
-}
-
-// What l12x6 itself lays out: the images in two fp16 parts (W1 image
-// [s][t][2 parts][lane][8], W2 image [m][2 parts][lane][8], two part rows
-// per pair-image row), behind the bias blocks the sample's scaled B2 and
-// twelve floats of maxima slots (max |W1| and max |W2|, one per wave, in the
-// prologue; max |X|, one per wave and sample), and the fp32 tile holding
-// x 2^ex.  The stride is padded for the tiles X6Lds pads (rs = 4 (ow / 4) mod
-// 32), else 2 w; the bytes never pass X6Lds's.
-constexpr int kH6W1 = kX6KS * 2 * 2 * 512;  // W1 image, fp16
-constexpr int kH6W2 = 4 * 2 * 512;          // W2 image, fp16
-constexpr int kH6Cst = 128 + 32 + 32 + 12;  // floats: [W1 tap 80 | B1], B2, the sample's B2, slots
-struct H6Lds {
-  int rs, r, xs, a2sc, bytes;  // pair-image row stride (dwords); byte offsets
-  __host__ __device__ H6Lds(int w, int h) {
-    const int a4 = (4 * ((w - 8) / 4)) % 32;
-    r = (kH6W1 + kH6W2) * 2 + kH6Cst * 4;
-    rs = X6Lds(w, h).pad ? 2 * w + ((a4 - 2 * w) % 32 + 32) % 32 : 2 * w;
-    xs = r + (rs * h + 1) * 4;
-    a2sc = (xs + w * h * 4 + 15) & ~15;
-    bytes = a2sc + 4 * kX6Sc * 4;
-  }
-};
 
 template <bool kLazy>
 __global__ __launch_bounds__(256, 2) void l12x6_fwd_kernel(const float* __restrict__ X,

@@ -1,5 +1,6 @@
 // l3_delta.hpp -- fused kernel 2 of train_fused.hip (included inside
-// namespace srcnn::fused): per sample, with the A2 tile resident in LDS,
+// namespace srcnn::fused after fused_layout.hpp: its LDS layout L3Lds, the
+// kL3* sizes, L3Geom; uses train_fused.hip's g_clk and kNtMask): per sample, with the A2 tile resident in LDS,
 //   L3 forward       layer_uber_kernel.cl:70-91 (SKIP_RELU)
 //   last delta       last_layer_delta.cl:34-48 (relu' quirk on a linear layer)
 //   squared error    squared_error.cl:60-69 (validation metric)
@@ -29,48 +30,12 @@
 // reads first.
 __device__ __forceinline__ int l3_order(int s, int batch) { return batch - 1 - s; }
 
-struct L3Geom {
-  int W, H;     // ground-truth sample (= network input size)
-  int w2, h2;   // A2
-  int w3, h3;   // A3
-  int batch;
-};
-
-// (768 / 1024 threads per block measured slower: the three barrier-separated
-// phases, not occupancy, set the pace)
-constexpr int kL3Threads = 512;
-constexpr int kL3TPF = (1024 + kL3Threads - 1) / kL3Threads;  // L3 outputs per thread (w3 * h3 <= 1024)
-constexpr int kL3MaxOut = kL3TPF * kL3Threads;
-
 // float index of A2[p][n] in the swizzled LDS image
 template <int N2>
 __device__ __forceinline__ int a2_at(int p, int n) {
   constexpr int NQ = N2 / 4;
   return p * N2 + 4 * ((n >> 2) ^ ((p >> 1) & (NQ - 1))) + (n & 3);
 }
-
-// LDS geometry shared by host and device (floats)
-template <int N2, int F3>
-struct L3Lds {
-  // 16-pixel units per wave of the largest A2 tile whose two regions fit the
-  // 160 KB LDS (npx2 * max(N2, F3^2) <= 20480 floats)
-  static constexpr int kMaxPx = 20480 / (N2 > F3 * F3 ? N2 : F3 * F3);
-  static constexpr int kUnitsPerWave = ((kMaxPx + 15) / 16 + kL3Threads / 64 - 1) / (kL3Threads / 64);
-  int region;  // one ping-pong region: max(A2 tile, Q of whole units, reduction scratch)
-  int d3off;   // delta3 grid offset (F3-1) * (w2 + 1)
-  int nd3;     // delta3 grid size (zero tail covers chunk overrun)
-  __host__ __device__ L3Lds(int w2, int h2) {
-    const int npx2 = w2 * h2, nch = (npx2 + 31) / 32;
-    int r = npx2 * N2;
-    const int npad = (npx2 + 15) / 16 * 16;  // Q is written for whole 16-pixel units
-    if (npad * F3 * F3 > r) r = npad * F3 * F3;
-    if (((N2 + 31) / 32) * 1024 > r) r = ((N2 + 31) / 32) * 1024;
-    region = (r + 3) & ~3;
-    d3off = (F3 - 1) * (w2 + 1);
-    nd3 = nch * 32 + d3off + 4;
-  }
-  __host__ __device__ size_t bytes() const { return (2 * (size_t)region + nd3) * sizeof(float); }
-};
 
 template <int N2, int F3>
 __global__ __launch_bounds__(kL3Threads, 1) void l3_delta_kernel(
@@ -416,9 +381,4 @@ __global__ __launch_bounds__(kL3Threads, 1) void l3_delta_kernel(
     out[NW3] = tb;
     sq_slab[blockIdx.x] = ts;
   }
-}
-
-template <int N2, int F3>
-static size_t l3_lds_bytes(int w2, int h2) {
-  return L3Lds<N2, F3>(w2, h2).bytes();
 }

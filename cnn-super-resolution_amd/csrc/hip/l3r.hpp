@@ -1,6 +1,8 @@
 // l3r.hpp -- fused kernel 2 of train_fused.hip for n2 = 32 (round 4; included
-// inside namespace srcnn::fused after l3_delta.hpp).  Same mathematics and
-// outputs as l3_delta_kernel:
+// inside namespace srcnn::fused after fused_layout.hpp -- its LDS layout
+// L3RLds, the kL3R* sizes, L3Geom -- and l3_delta.hpp, whose l3_order it
+// shares; uses train_fused.hip's g_clk).  Same mathematics and outputs as
+// l3_delta_kernel:
 //   L3 forward       layer_uber_kernel.cl:70-91 (SKIP_RELU), Q trick
 //   last delta       last_layer_delta.cl:34-48 (relu' quirk on a linear layer)
 //   squared error    squared_error.cl:60-69
@@ -31,14 +33,6 @@
 // n2 = 32 and tiles of up to 40 16-pixel units (625-pixel A2: 33x33 samples
 // at f1 = 9); other shapes keep l3_delta_kernel.
 
-constexpr int kL3RThreads = 512;
-constexpr int kL3RUnits = 5;  // 16-pixel units per wave (8 waves: 640 pixels)
-constexpr int kL3RTPF = 1;    // L3 outputs per thread (w3 * h3 <= 512 for every A2 tile of <= 640 pixels)
-constexpr int kL3RW3S = 36;   // W3 image row stride (floats): conflict-free 16-B reads
-constexpr int kL3RScS = 36;   // transpose scratch row stride (floats) per channel
-
-constexpr int kL3RWdS = 36;   // delta2 W3 image row stride (floats): 4 groups x 8 slots + pad
-
 // delta2 k-slot (s, lg) -> tap, chosen so that the delta3 window offset of a
 // slot is a per-lane base plus an immediate: for s < F3, lane group lg takes
 // tap row dy = lg, dx = s; f3 = 5 puts row 4 in slots s = 5, 6 (dx = 4(s-5) + lg).
@@ -50,48 +44,6 @@ __host__ __device__ constexpr int l3r_tap(int s, int lg) {
 }
 template <int F3>
 constexpr int l3r_kt() { return F3 == 5 ? 7 : F3; }
-
-template <int F3>
-struct L3RLds {
-  int qreg;   // Q image [640][F3^2] (every unit slot); aliased by the transpose scratch and the final reduction
-  int w3img;  // W3 image [tap][kL3RW3S] (Q's B operand)
-  int wdimg;  // W3 image [c][h][lg][4] at row stride kL3RWdS (delta2's A operand; slot s = 4h + i)
-  int d3off;  // delta3 grid offset (F3-1) * (w2 + 1)
-  int nd3;    // delta3 grid size, after a 4-float zero lead (unused slots read below the grid)
-  __host__ __device__ L3RLds(int w2, int h2) {
-    // every wave runs all kL3RUnits unit slots (no data-dependent branches
-    // around the A2 loads: the compiler's wait-count pass would then lose
-    // track of them and wait for every load right after issuing it), so the
-    // Q image and the delta3 grid cover all 8 * kL3RUnits units
-    (void)h2;
-    constexpr int npad = 16 * 8 * kL3RUnits;
-    int r = npad * F3 * F3;
-    if (r < 8 * 32 * kL3RScS) r = 8 * 32 * kL3RScS;
-    if (r < 8 * 2 * 2 * 4 * 64) r = 8 * 2 * 2 * 4 * 64;  // the final reduction (8 waves x 16 x 64)
-    qreg = (r + 3) & ~3;
-    w3img = (F3 * F3 * kL3RW3S + 3) & ~3;
-    wdimg = 32 * kL3RWdS;
-    d3off = (F3 - 1) * (w2 + 1);
-    nd3 = 4 + ((npad + d3off + 4 + 3) & ~3);
-  }
-  __host__ __device__ size_t bytes() const { return ((size_t)qreg + w3img + wdimg + nd3) * sizeof(float); }
-};
-
-// the shapes l3r takes: two blocks per CU, whole units per wave
-template <int F3>
-static bool l3r_fits(int w2, int h2, int w3, int h3) {
-  const int nunit = (w2 * h2 + 15) / 16;
-  return nunit <= 8 * kL3RUnits && w3 * h3 <= kL3RThreads * kL3RTPF &&
-         L3RLds<F3>(w2, h2).bytes() <= 80 * 1024;
-}
-
-// kD3Out also keeps gW3's split delta3 pair images (3 x nd3 dwords) in the Q
-// image past the transpose scratches
-template <int F3>
-static bool l3r_d3_fits(int w2, int h2) {
-  const L3RLds<F3> L(w2, h2);
-  return 8 * 32 * kL3RScS + 3 * L.nd3 <= L.qreg;
-}
 
 // A2 loads and D2 stores with the nontemporal hint (A2 is read once here,
 // D2 once by d1): l3 0.1578 / 0.1577 -> 0.1555 / 0.1552 ms against plain

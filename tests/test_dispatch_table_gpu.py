@@ -3,8 +3,10 @@ family (srcnn_last_path) and which kernel variants, in launch order
 (srcnn_last_kernels), serve each net / tile under either arithmetic.  The
 table, tests/golden/dispatch_table.json, is recorded on the MI355X by
 tools/record_dispatch_table.py; the comparison is exact list equality.  The
-plans that decide all of this are plan_step / plan_forward of train_fused.hip,
-wide_plan.hpp (the wide family, train_wide.hip) and forward_fused.hip."""
+plans that decide all of this are plan_step of fused_plan.hpp (the fused
+family, train_fused.hip; its names are compared with the table on the host
+too, tests/test_fused_plan_cpu.py), plan_step of wide_plan.hpp (the wide
+family, train_wide.hip) and plan_forward of forward_fused.hip."""
 import importlib.util
 import json
 import os
