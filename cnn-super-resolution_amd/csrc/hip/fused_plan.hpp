@@ -1,33 +1,16 @@
 // fused_plan.hpp -- what the fused family decides on the host before a
 // launch: the nets it serves and the step's plan.  Included inside namespace
-// srcnn::fused after fused_layout.hpp; host code without any HIP call
+// srcnn::fused after fused_layout.hpp; includes net.hpp (Net, first_net) itself,
+// as fused_layout.hpp includes runs.hpp, so whoever includes the plan needs no
+// further header.  Host code without any HIP call
 // (tests/fused_plan_check.cpp prints and checks every plan on the CPU).  Two
 // quantities come from other units, as declared calls (ops.hpp): the op-level
 // layer-3 gradient workspace (fast::grad_workspace_bytes) and the squared-error
 // reduction's blocks (reduce_blocks), for tiles whose layer 3 runs on the
 // op-level kernels.
+#include "net.hpp"
 
-template <int N1_, int N2_, int F1_, int F3_>
-struct Net {
-  static constexpr int N1 = N1_, N2 = N2_, F1 = F1_, F3 = F3_;
-  static constexpr int P12 = F1 * F1 * N1 + N1 + N1 * N2 + N2;
-  static constexpr int P3 = F3 * F3 * N2 + 1;
-  // layers 1-2 of the default net: the split-bf16 pair and d1c are built for them
-  static constexpr bool kDefault12 = N1 == 64 && N2 == 32 && F1 == 9;
-};
-
-// The instantiated nets, once: f(Net<..>{}) of the one that `net` is, else 0.
-// plan, run and preload all dispatch through here.
-template <typename F, typename... Ns>
-static int first_net(const srcnn_net* net, F&& f, Ns... ns) {
-  int rc = 0;
-  auto is = [&](auto n) {
-    return net->n1 == (uint32_t)n.N1 && net->n2 == (uint32_t)n.N2 && net->f1 == (uint32_t)n.F1 &&
-           net->f2 == 1 && net->f3 == (uint32_t)n.F3;
-  };
-  (void)((is(ns) && (rc = f(ns), true)) || ...);
-  return rc;
-}
+// The instantiated nets, once.
 template <typename F>
 static int with_net(const srcnn_net* net, F&& f) {
   return first_net(net, f, Net<64, 32, 9, 5>{},  // reference default (BASELINE.json configs[1])

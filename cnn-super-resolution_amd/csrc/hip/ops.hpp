@@ -88,9 +88,10 @@ bool train_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, St
 // of accumulating.  b.D1 is not used.
 int train_fwd_bwd(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, const StepBuffers& b,
                   hipStream_t s, const SlabUpdate* up, const LazyUpdate* lz);
-// Fused inference (forward_fused.hip): forward_plan tells whether the net is
-// served and the workspace bytes (FwdPlan); forward returns 1 when it ran,
-// 0 when the net is not served, < 0 on error.
+// Fused inference (forward_fused.hip; the plan is FwdPlan of fwd_plan.hpp):
+// forward_plan tells whether the net and frame are served under the current
+// arithmetic and the workspace bytes (the plan's part_bytes); forward returns
+// 1 when it ran, 0 when they are not served, < 0 on error.
 bool forward_plan(const srcnn_net* net, uint32_t w, uint32_t h, uint32_t batch, size_t* ws_bytes);
 int forward(const srcnn_net* net, const float* X, uint32_t w, uint32_t h, uint32_t batch,
             const float* params, float* out, void* ws, size_t ws_bytes, hipStream_t s);

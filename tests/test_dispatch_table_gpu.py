@@ -6,7 +6,7 @@ tools/record_dispatch_table.py; the comparison is exact list equality.  The
 plans that decide all of this are plan_step of fused_plan.hpp (the fused
 family, train_fused.hip; its names are compared with the table on the host
 too, tests/test_fused_plan_cpu.py), plan_step of wide_plan.hpp (the wide
-family, train_wide.hip) and plan_forward of forward_fused.hip."""
+family, train_wide.hip) and plan_forward of fwd_plan.hpp (forward_fused.hip)."""
 import importlib.util
 import json
 import os

@@ -2,7 +2,7 @@
 # A/B of library variants on the training step AND the 4K forward:
 #   tools/ab_fwd.sh <tag> <lib1.so> [lib2.so ...]
 # Each variant first passes the fused train-step + frame-forward parity tests,
-# then is benched twice (interleaved) to expose run-to-run noise.
+# then is benched REPS times (default 2, interleaved) to expose run-to-run noise.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:-abf}; shift
@@ -15,7 +15,7 @@ for lib in "$@"; do
   rc=$?; echo "variant $i ($lib) pytest rc=$rc: $(tail -1 $OUT/pytest_$i.log)"
   [ $rc -eq 0 ] || exit $rc
 done
-for rep in 1 2; do
+for rep in $(seq 1 ${REPS:-2}); do
   i=0
   for lib in "$@"; do
     i=$((i+1))
