@@ -29,12 +29,15 @@
 //                  pair images (row runs: R; column runs: T, column-major)
 //                  kD3: in two fp16 parts per operand instead (split.hpp),
 //                  three v_mfma_f32_32x32x16_f16 per k-step where the bf16
-//                  form takes six: delta1 2^e1 and X 2^ex with per-sample
-//                  exponents from bounds (max |delta3| times the two weight
-//                  norms; max |X|), the accumulators 2^EW x the sum (the bias
-//                  column 2^EB x), unscaled in the block reduction.  The X
-//                  images keep their layout and use dwords 0 and 1 of a
-//                  position's three
+//                  form takes six: delta1 2^e1 and X 2^ex with one pair of
+//                  exponents for the launch, from bounds over all its samples
+//                  (max |delta3| times the two weight norms; max |X|: the
+//                  per-block maxima that l3r and l12x6 leave behind the mask,
+//                  reduced in the prologue), the accumulators 2^(e1 + ex) x
+//                  the sum (the bias column 2^e1 x), unscaled in the block
+//                  reduction; a sample's top is its image builds and one
+//                  barrier.  The X images keep their layout and use dwords 0
+//                  and 1 of a position's three
 //   gB2[n] += sum_p delta2[p][n]                     VALU over delta2^T (kTr:
 //                  per lane over the rows, crossed over lanes in the epilogue)
 // Each wave accumulates over its chunks; at the end the four waves' sums are
@@ -43,16 +46,10 @@
 // 30 MB written and read back per step.)
 // One wave per SIMD (512 registers: 128 accumulators + operands).
 
-// kD3: the waves' per-sample maxima in the constant region (dword offsets)
+// kD3: the waves' launch maxima in the constant region (dword offsets).
+// (gW1's accumulators cannot overflow under the launch's scales: 2^30 per
+// product, < 2^20 slots per wave)
 constexpr int kD6Mxx = 12, kD6Mx3 = 25;
-// kD3: gW1's accumulators hold 2^EW x the sum (the bias column 2^EB x); a
-// sample whose own exponent lies within this window of EW takes its X scale
-// from EW, one outside it moves EW (the accumulators are multiplied by the
-// exact power of two) to kD6ExMid below its own
-constexpr int kD6ExWin = 6, kD6ExMid = 3;
-// no sample's scale lies more than 2^kD6Grow above the largest sample's seen
-// (the accumulators cannot overflow: 2^30 per product, < 2^20 slots per wave)
-constexpr int kD6Grow = 70;
 
 // the all-zero delta2 row that dummy slots load (runs.hpp: slots past the
 // tile), with the lane-half offset and the four 16-B quads of a real row
@@ -120,6 +117,8 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
                                                               const float* __restrict__ D2,
                                                               const float* __restrict__ A2,
                                                               const uint32_t* __restrict__ M2,
+                                                              const float* __restrict__ xmaxs,
+                                                              const float* __restrict__ d3maxs, D6MaxGeom mg,
                                                               const float* __restrict__ W2,
                                                               const float* __restrict__ W3,
                                                               float* __restrict__ slab, Geom g, RunGeom rg,
@@ -152,6 +151,20 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     }
   };
   if ((int)blockIdx.x < g.batch) xload(blockIdx.x);
+  // kD3: the launch's maxima of |X| (one slot per l12x6 block with a sample)
+  // and of |delta3| (per l3r block), two slots of each per thread, in flight
+  // with the W2 / W3 loads below.  Only the written slots are read.
+  float lmx = 0.0f, lm3 = 0.0f;
+  if constexpr (kD3) {
+    static_assert(kL12Grid <= 512 && kL3RGrid <= 512, "two slots per thread");
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const int i = threadIdx.x + 256 * k;
+      const float a = i < mg.n12 ? xmaxs[i] : 0.0f, b = i < mg.n3 ? d3maxs[i] : 0.0f;
+      lmx = fmaxf(lmx, a);
+      lm3 = fmaxf(lm3, b);
+    }
+  }
 
   // ---- per-block tables and images ----
   if constexpr (!kTr)
@@ -172,12 +185,14 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   // gW1's third tap tile past tap 80: the ones column (gB1) and zero columns
   // read these constant pair images instead of X (dwords q and q + 6 of part q)
   // kD3 (gW1 in two fp16 parts, below): two ones images, at dwords 0 and 3
-  // (sample parity; dwords q, q + 6 of part q < 2), whose constant 2^k each
-  // sample writes at its top; the zero image from dword 16; dwords 12-15 and
-  // 25-28 hold the waves' maxima of |X| and |delta3| (kD6Mxx, kD6Mx3: written
-  // before this store may land, so it leaves them out)
-  if (threadIdx.x < 32 && (!kD3 || threadIdx.x < kD6Mxx || (threadIdx.x >= 16 && threadIdx.x < kD6Mx3)))
-    u32[L.cst / 4 + threadIdx.x] = !kD3 && (threadIdx.x == 0 || threadIdx.x == 6) ? 0x3F803F80u : 0u;
+  // (sample parity; dwords q, q + 6 of part q < 2), both the fp16 pair 1.0
+  // (the bias column carries delta1's scale alone); the zero image from dword
+  // 16; dwords 12-15 and 25-28 hold the waves' maxima of |X| and |delta3|
+  // (kD6Mxx, kD6Mx3: written before this store may land, so it leaves them out)
+  if (threadIdx.x < 32 && (!kD3 || threadIdx.x < kD6Mxx || (threadIdx.x >= 16 && threadIdx.x < kD6Mx3))) {
+    const bool one = threadIdx.x == 0 || threadIdx.x == 6 || (kD3 && (threadIdx.x == 3 || threadIdx.x == 9));
+    u32[L.cst / 4 + threadIdx.x] = one ? (kD3 ? 0x3C003C00u : 0x3F803F80u) : 0u;
+  }
   {
     // delta1's B operand W2^T: tile t, k-step k, lane (c, h), element j <->
     // W2[32 t + c][n] with n = 16 k + 8 h + j (delta2 rows as loaded), or for
@@ -233,10 +248,16 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     }
   };
   // kD3: gW1 / gB1 in two fp16 parts per operand (split.hpp: three MFMAs per
-  // k-step where the bf16 form takes six).  Each sample's delta1 is scaled by
-  // 2^e1 from the bound |delta1| <= max |delta3| . max_n sum_tap |W3[tap][n]| .
-  // max_c sum_n |W2[c][n]| and its X by 2^ex from max |X|; both maxima are
-  // block maxima through the constant region (one more barrier per sample).
+  // k-step where the bf16 form takes six).  delta1 is scaled by 2^e1 from the
+  // bound |delta1| <= max |delta3| . max_n sum_tap |W3[tap][n]| . max_c sum_n
+  // |W2[c][n]| and X by 2^ex from max |X|, both maxima over the whole launch
+  // (l3r's and l12x6's per-block maxima, reduced here through the constant
+  // region behind the prologue's barrier): gW1 and gB1 are sums over the
+  // launch, a power of two leaves an operand's parts as they are while none is
+  // subnormal, and a sample more than 2^17 below the largest loses low bits
+  // at 2^-39 of the largest one's terms.  The accumulators hold 2^EW x the sum
+  // (EW = e1 + ex; the bias column 2^EB x, EB = e1), unscaled in the block
+  // reduction.
   float* const mxx = smem + L.cst / 4 + kD6Mxx;
   float* const mx3 = smem + L.cst / 4 + kD6Mx3;
   auto wave_max = [&](float v) {
@@ -256,8 +277,9 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     const float v = fmaxf(fmaxf(slot[0], slot[1]), fmaxf(slot[2], slot[3]));
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
   };
-  float m3cur = 0.0f, wnorm = 0.0f;  // max |delta3| of the current sample; the two norms' product
-  int EW = 0, EB = 0, EWmin = 1 << 20, EBmin = 1 << 20;
+  float wnorm = 0.0f;  // the two norms' product
+  int EW = 0, EB = 0;
+  float s1 = 1.0f, sX = 1.0f;  // kD3: 2^e1 for delta1, 2^ex for X
   if constexpr (kD3) {
     {
       // (every wave forms both norms itself: lane = W2's channel, lane & 31 = W3's)
@@ -305,9 +327,19 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
     for (int i = threadIdx.x; i < (3 * L.d3buf + 3) / 4; i += 256)  // borders stay zero
       reinterpret_cast<uint4*>(d3u)[i] = uint4{0u, 0u, 0u, 0u};
     if ((int)blockIdx.x < g.batch) d3load(blockIdx.x);
-    put_max(mx3, fmaxf(fabsf(d3n[0]), fabsf(d3n[1])));
+    put_max(mxx, lmx);
+    put_max(mx3, lm3);
     __syncthreads();  // zeroed before the first build
-    m3cur = take_max(mx3);
+    {
+      // the launch's scales (the same scalars on every thread)
+      const float xmax = take_max(mxx), bound = take_max(mx3) * wnorm;
+      // (a zero bound: delta1 = 0 throughout, any finite scale does; zero X alike)
+      const int e1 = bound > 0.0f ? mfma::scale_exp_h(bound) : 0, ex = xmax > 0.0f ? mfma::scale_exp_h(xmax) : 0;
+      EW = e1 + ex;
+      EB = e1;
+      s1 = mfma::pow2_h(e1);
+      sX = mfma::pow2_h(ex);
+    }
     d3build(0);       // sample 0 (buffer j % 3 holds sample j)
     if ((int)blockIdx.x + (int)gridDim.x < g.batch) d3load(blockIdx.x + gridDim.x);
   }
@@ -587,92 +619,17 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
   for (int it = 0; (int)blockIdx.x + it * (int)gridDim.x < g.batch; it++) {
     const int smp = blockIdx.x + it * gridDim.x;
     uint32_t* const xi = xbuf + (it & 1) * L.xbuf;
-    // ---- kD3: this sample's scales (the same scalars on every thread) ----
-    float s1 = 1.0f, sX = 1.0f;  // 2^e1 for delta1, 2^ex for X
-    float m3next = 0.0f;
+    // kD3: sample it + 1's delta3 image into buffer (it + 1) % 3, last read for
+    // sample it - 2 (every wave is past that sample: the barrier at the top of
+    // sample it - 1); read from the first delta2 of sample it + 1 on, after
+    // the barrier below
     if constexpr (kD3) {
-      float xm = 0.0f;
-#pragma unroll
-      for (int k = 0; k < kL12Regs; k++) xm = fmaxf(xm, fabsf(xr[k]));
-      // (the two reductions step by step together: one after the other they
-      // were twelve dependent LDS round trips at every sample's top)
-      float dm = fmaxf(fabsf(d3n[0]), fabsf(d3n[1]));  // sample it + 1's, if there is one
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float tx = __shfl_xor(xm, o, 64), td = __shfl_xor(dm, o, 64);
-        xm = fmaxf(xm, tx);
-        dm = fmaxf(dm, td);
-      }
-      if (lane == 0) {
-        mxx[wave] = xm;
-        mx3[wave] = dm;
-      }
-      // sample it + 1's delta3 image into buffer (it + 1) % 3, last read for
-      // sample it - 2 (every wave is past that sample: the barrier at the top
-      // of sample it - 1); read from the first delta2 of sample it + 1 on,
-      // after the second barrier below.  (Ahead of the first: it does not wait
-      // for the scales)
       if (smp + (int)gridDim.x < g.batch) d3build((it + 1) - 3 * ((it + 1) / 3));
-      __syncthreads();  // (the slots are written again after the barrier below, read before it)
-      const float xmax = take_max(mxx);
-      m3next = take_max(mx3);
-      const float bound = m3cur * wnorm;
-      // (exn >= -123: 2^(exn - kD6ExMid) stays a normal fp32)
-      int e1 = mfma::scale_exp_h(bound), exn = mfma::scale_exp_h(xmax), ex = 0, kb = 0, dW = 0, dB = 0;
-      if (exn < mfma::kScaleMin + kD6ExMid) exn = mfma::kScaleMin + kD6ExMid;
-      if (bound > 0.0f) {
-        // a sample far below the largest seen takes a smaller scale
-        int exc = e1 + exn - kD6ExMid - (EWmin + kD6Grow);
-        if (exc < e1 - (EBmin + kD6Grow)) exc = e1 - (EBmin + kD6Grow);
-        if (exc > 0) e1 = e1 - exc < mfma::kScaleMin ? mfma::kScaleMin : e1 - exc;
-        // the bias column's constant 2^kb (a normal fp16) takes up EB - e1, or EB moves
-        kb = EB - e1;
-        if (kb < -14 || kb > 15) {
-          dB = e1 - EB;
-          EB = e1;
-          kb = 0;
-        }
-        if (xmax > 0.0f) {
-          ex = EW - e1;
-          if (ex > exn || ex < exn - kD6ExWin) {
-            ex = exn - kD6ExMid;
-            dW = e1 + ex - EW;
-            EW = e1 + ex;
-          }
-        }
-        if (EW < EWmin) EWmin = EW;
-        if (EB < EBmin) EBmin = EB;
-      } else {
-        e1 = 0;  // delta1 = 0 throughout: any finite scales do
-        ex = xmax > 0.0f ? exn - kD6ExMid : 0;
-      }
-      s1 = mfma::pow2_h(e1);
-      sX = mfma::pow2_h(ex);
-      if (threadIdx.x == 0) {
-        const uint32_t c = (uint32_t)(kb + 15) << 10;  // 2^kb as fp16
-        u32[L.cst / 4 + 3 * (it & 1)] = u32[L.cst / 4 + 3 * (it & 1) + 6] = c | (c << 16);
-      }
-      // the accumulators to the new exponents, in exact steps of at most 2^120
-      while (dW != 0 || dB != 0) {
-        const int a = dW < -120 ? -120 : dW > 120 ? 120 : dW, b = dB < -120 ? -120 : dB > 120 ? 120 : dB;
-        const float fw = mfma::pow2_h(a), fb = li == K1 - 64 ? mfma::pow2_h(b) : fw;
-        // (one tile at a time: all 96 registers at once spilled the item loop's state)
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-          for (int u = 0; u < 3; u++) {
-            const float f = u == 2 ? fb : fw;
-#pragma unroll
-            for (int r = 0; r < 16; r++) g1[t][u][r] *= f;
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        dW -= a;
-        dB -= b;
-      }
     }
     // ---- this sample's X pair images (buffer it & 1) ----
     if constexpr (kD3) {
-      // (two fp16 parts of X 2^ex in dwords 0 and 1 of a position's three)
+      // (two fp16 parts of X 2^ex in dwords 0 and 1 of a position's three;
+      // buffer it & 1 was last read for sample it - 2, as the delta3 buffer)
       uint16_t* const x16 = reinterpret_cast<uint16_t*>(xi);
 #pragma unroll
       for (int k = 0; k < kL12Regs; k++) {
@@ -718,7 +675,9 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
         }
       }
     }
-    __syncthreads();  // images (and at it == 0 the tables) complete; buffer (it+1)&1 free
+    // images (and at it == 0 the tables) complete; every wave is past sample
+    // it - 1: X buffer (it+1)&1 and delta3 buffer (it+2)%3 are free
+    __syncthreads();
     const int nsmp = smp + (int)gridDim.x;
     if (nsmp < g.batch) xload(nsmp);
     if constexpr (kD3) {
@@ -978,7 +937,6 @@ __global__ __launch_bounds__(256, 1) void d1x6_grad12_kernel(const float* __rest
       kj = nj;
       kc = nc;
     }
-    m3cur = m3next;
   }
   SRCNN_CLOCK_END(g_clk, 2);
 

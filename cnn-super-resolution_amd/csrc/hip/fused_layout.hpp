@@ -206,6 +206,11 @@ constexpr int kD6Sc = 32 * 36;           // per-wave delta2 transpose scratch (f
 struct D3Geom {
   int w3, h3, f3;
 };
+// kD3: how many slots of the launch maxima were written (the blocks of l12x6
+// and of l3r that had a sample: min(grid, batch) each)
+struct D6MaxGeom {
+  int n12, n3;
+};
 
 struct D6Lds {
   int st;      // T image column stride (dwords per column, >= 4 cr + 9)

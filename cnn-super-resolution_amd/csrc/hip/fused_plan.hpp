@@ -38,6 +38,10 @@ struct StepPlan {
   size_t s12, s3, ssq;       // slab regions in floats: layers 1-2 | layer 3 | squared error
   size_t bytes;              // the three in bytes
   size_t m2_off;             // d3mode: dwords from D2 to the mask (delta3 first, 256-B aligned)
+  // d3mode: dwords from D2 to the launch maxima behind the mask (256-B aligned
+  // each): one max |X| per l12x6 block at mx_off, one max |delta3| per l3r
+  // block at d3mx_off (d1x6.hpp: its launch scale)
+  size_t mx_off, d3mx_off;
   int a1_layout;             // what l12 writes: kA1Runs or kA1Blocked
   // the names the step notes (srcnn_last_kernels): l12's without the lazy
   // suffix, layer 3's, delta1's
@@ -84,8 +88,14 @@ static bool plan_step(uint32_t w, uint32_t h, uint32_t batch, int arith, StepPla
   // delta3 and the mask (one dword per A2 pixel) fit the region sized for
   // delta2 (ow * oh * N2 floats per sample)
   p.m2_off = ((size_t)batch * w3 * h3 + 63) & ~(size_t)63;
+  // (the maxima always fit where the mask does: they end within (2 ow oh + 1)
+  // batch + 3 x 63 + kL3RGrid dwords, and a d3mode tile has nch >= 4, ow oh > 96;
+  // no served tile changes its mode by the last condition)
+  p.mx_off = (p.m2_off + (size_t)batch * ow * oh + 63) & ~(size_t)63;
+  p.d3mx_off = (p.mx_off + p.g12 + 63) & ~(size_t)63;
   p.d3mode = p.x6 && p.l3r && F3 <= 5 && d1x6_fits(w, h, true) && l3r_d3_fits<F3>(ow, oh) &&
-             p.m2_off + (size_t)batch * ow * oh <= (size_t)batch * ow * oh * N2;
+             p.m2_off + (size_t)batch * ow * oh <= (size_t)batch * ow * oh * N2 &&
+             p.d3mx_off + kL3RGrid <= (size_t)batch * ow * oh * N2;
   const int gd6 = grid_for_batch(batch, 256);  // d1x6
   const int gdf = p.kD1c ? (int)std::min<size_t>((size_t)batch * p.d1c_parts, kD1cGrid) : grid_for_batch(batch, 512);
   p.gd = p.x6 ? gd6 : gdf;

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void l12x6_fwd_kernel(const float* __restri
                                                             const float* __restrict__ B2,
                                                             float* __restrict__ A1,
                                                             float* __restrict__ A2, Geom g, RunGeom rg,
-                                                            LazyUpdate lz) {
+                                                            LazyUpdate lz, float* __restrict__ xmax) {
   constexpr int N1 = 64, N2 = 32, F1 = 9, NT1 = 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const H6Lds L(g.W, g.H);
@@ -281,6 +281,9 @@ __global__ __launch_bounds__(256, 2) void l12x6_fwd_kernel(const float* __restri
     for (int q = 0; q < 2; q++) a[q] = *reinterpret_cast<const f16x8*>(wl1 + ((s * 2 + t) * 2 + q) * 512);
   };
 
+  // the largest max |X| over this block's samples, for d1x6's launch scale
+  // (xmax: one slot per block, or null)
+  float xrun = 0.0f;
   for (int sample = blockIdx.x; sample < g.batch; sample += gridDim.x) {
     // The sample's scale: ex = scale_exp_h(max |X|) from the registers that
     // hold it, a wave reduction and one slot per wave.  The slots are
@@ -296,6 +299,7 @@ __global__ __launch_bounds__(256, 2) void l12x6_fwd_kernel(const float* __restri
     }
     __syncthreads();  // previous sample's readers are done with the images
     const int ex = mfma::scale_exp_h(max4(xmx));
+    xrun = fmaxf(xrun, max4(xmx));
     const float sx = mfma::pow2_h(ex);
     // the accumulators carry 2^(ew + ex); -(ew + ex) lies in [-120, 228], so
     // the factor is taken out in one exact step, or two where it passes 2^127
@@ -464,5 +468,7 @@ __global__ __launch_bounds__(256, 2) void l12x6_fwd_kernel(const float* __restri
   // (a sample's last chunk is stored under the next sample's first one)
 #pragma unroll
   for (int k = 0; k < NST; k++) store_prev(k);
+  // (a block without a sample writes nothing: d1x6 reads the first min(grid, batch) slots)
+  if (xmax != nullptr && threadIdx.x == 0 && (int)blockIdx.x < g.batch) xmax[blockIdx.x] = xrun;
   SRCNN_CLOCK_END(g_clk, 0);
 }

@@ -60,12 +60,14 @@ __device__ __forceinline__ void st_d2(float* p, f32x4 v) {
 // from it (d1x6.hpp), so the 328 MB of delta2 per 4096-tile step never make
 // an HBM round trip and this kernel keeps Q, the window sums and gW3.  It
 // also writes M2, layer 2's relu' mask as one dword per A2 pixel (bit n =
-// A2[pixel][n] > 0), so d1x6 need not read A2 for it.
+// A2[pixel][n] > 0), so d1x6 need not read A2 for it, and d3max[block], the
+// largest |delta3| over the block's samples, for d1x6's launch scale.
 template <int F3, bool kD3Out>
 __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wave blocks per CU (128 VGPRs)
     const float* __restrict__ A2, const float* __restrict__ T, const float* __restrict__ W3,
     const float* __restrict__ B3, float* __restrict__ D2, float* __restrict__ slab3,
-    float* __restrict__ sq_slab, float* __restrict__ A3out, uint32_t* __restrict__ M2, L3Geom g) {
+    float* __restrict__ sq_slab, float* __restrict__ A3out, uint32_t* __restrict__ M2,
+    float* __restrict__ d3max, L3Geom g) {
   constexpr int N2 = 32;
   constexpr int K3 = F3 * F3;
   constexpr int TT = (K3 + 15) / 16;  // 16-wide tap tiles
@@ -179,6 +181,7 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
   const int g3b = d3off - tap_off(li32 < K3 ? li32 : 0) + 16 * wave + 8 * h32;
   const int g3s = li32 * kL3RScS + 8 * h32;
   float gb3 = 0.0f, sq = 0.0f;
+  float dmx = 0.0f;  // kD3Out: this thread's largest |delta3|
 
   // this lane's A2 registers: unit j = wave + 8j, pixel 16u + lq, channel
   // quads lg and 4 + lg.  Past the sample's pixels a lane loads pixel lq
@@ -336,7 +339,10 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
         const float diff = a3 - tcur[k];
         const float d3 = diff * (a3 > 0.0f ? 1.0f : 0.0f);
         d3g[y * g.w2 + x + d3off] = d3;
-        if constexpr (kD3Out) D2[(size_t)smp * nout + t] = d3;
+        if constexpr (kD3Out) {
+          D2[(size_t)smp * nout + t] = d3;
+          dmx = fmaxf(dmx, fabsf(d3));
+        }
         gb3 += d3;
         sq += diff * diff;
       }
@@ -549,11 +555,13 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
   for (int off = 32; off > 0; off >>= 1) {
     gb3 += __shfl_down(gb3, off, 64);
     sq += __shfl_down(sq, off, 64);
+    if constexpr (kD3Out) dmx = fmaxf(dmx, __shfl_down(dmx, off, 64));
   }
   __syncthreads();
   if (lane == 0) {
     red[2 * wave] = gb3;
     red[2 * wave + 1] = sq;
+    if constexpr (kD3Out) red[2 * nwaves + wave] = dmx;
   }
   __syncthreads();
   if (tid == 0) {
@@ -564,5 +572,11 @@ __global__ __launch_bounds__(kL3RThreads, 4) void l3r_delta_kernel(  // two 8-wa
     }
     out[NW3] = tb;
     sq_slab[blockIdx.x] = ts;
+    // (a block without a sample writes nothing: d1x6 reads the first min(grid, batch) slots)
+    if constexpr (kD3Out) {
+      float tm = 0.f;
+      for (int w = 0; w < nwaves; w++) tm = fmaxf(tm, red[2 * nwaves + w]);
+      if ((int)blockIdx.x < g.batch) d3max[blockIdx.x] = tm;
+    }
   }
 }

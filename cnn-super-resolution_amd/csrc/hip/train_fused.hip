@@ -34,7 +34,8 @@
 //                    sample's chunks in d1c_parts ranges.  The default layers
 //                    1-2, tiles up to 40 wide.  !x6 && kD1c
 //     d1x6.hpp       d1x6_grad12_kernel<d3, tr>: bf16 split products (gW1 on
-//                    two-part fp16 ones in the d3 form); <true, .> forms delta2
+//                    two-part fp16 ones in the d3 form, scaled once per launch
+//                    from the maxima l12x6 and l3r leave); <true, .> forms delta2
 //                    itself from l3r's delta3 (d3taps.hpp), <true, true> passes
 //                    delta2's parts through a bf16 image (d6tr.hpp).  x6; d3mode;
 //                    d1tr
@@ -149,6 +150,10 @@ static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, 
   const auto P = split_params(lazy ? lz->Po : b.params, net);
   const int ow = p.ow, oh = p.oh, w3 = p.w3, h3 = p.h3;
   const Geom g{(int)w, (int)h, ow, oh, (int)batch};
+  // d3mode: the launch maxima behind the mask in the D2 region, one slot per
+  // block of l12x6 (max |X|) and of l3r (max |delta3|), read by d1x6
+  float* const xmax = p.d3mode ? D2 + p.mx_off : nullptr;
+  float* const d3max = p.d3mode ? D2 + p.d3mx_off : nullptr;
   {
     SRCNN_PROFILE("l12_fwd_mfma", s);
     kernels_note(lazy ? (std::string(p.k12) + "_lazy").c_str() : p.k12);
@@ -157,7 +162,7 @@ static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, 
     const auto k6 = lazy ? l12x6_fwd_kernel<true> : l12x6_fwd_kernel<false>;
     const auto k = lazy ? l12_fwd_kernel<N1, N2, F1, true> : l12_fwd_kernel<N1, N2, F1>;
     // l12x6: 78 KB of LDS for 33x33 tiles, two blocks per CU
-    if (int rc = p.x6 ? launch(k6, grid, blk, p.lds12, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, p.rg, lu)
+    if (int rc = p.x6 ? launch(k6, grid, blk, p.lds12, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, p.rg, lu, xmax)
                       : launch(k, grid, blk, 0, s, X, P.W1, P.B1, P.W2, P.B2, A1, A2, g, lu))
       return rc;
   }
@@ -172,7 +177,7 @@ static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, 
     SRCNN_PROFILE("l3_delta_fused", s);
     const dim3 grid(p.g3);
     const auto kr = p.d3mode ? l3r_delta_kernel<F3, true> : l3r_delta_kernel<F3, false>;
-    if (int rc = p.l3r ? launch(kr, grid, dim3(kL3RThreads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, M2, lg)
+    if (int rc = p.l3r ? launch(kr, grid, dim3(kL3RThreads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, M2, d3max, lg)
                        : launch(l3_delta_kernel<N2, F3>, grid, dim3(kL3Threads), p.lds3, s, A2, T, P.W3, P.B3, D2, slab3, sqs, A3, lg))
       return rc;
   } else {
@@ -195,9 +200,10 @@ static int run(const StepPlan& p, const srcnn_net* net, uint32_t w, uint32_t h, 
     kernels_note(p.kd1);
     const dim3 grid(p.gd), blk(256);
     const D3Geom dg{w3, h3, F3};
+    const D6MaxGeom mg{p.g12, p.g3};  // the blocks of l12x6 and l3r, each with a sample
     // d1x6<true>: D2 holds delta3 and M2 the mask; A2 is not read then
     const auto k6 = p.d1tr ? d1x6_grad12_kernel<true, true> : p.d3mode ? d1x6_grad12_kernel<true> : d1x6_grad12_kernel<false>;
-    if (int rc = p.x6 ? launch(k6, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, P.W2, P.W3, slab12, g, p.rg, dg)
+    if (int rc = p.x6 ? launch(k6, grid, blk, p.ldsd, s, X, A1, D2, A2, M2, xmax, d3max, mg, P.W2, P.W3, slab12, g, p.rg, dg)
                  : p.kD1c ? launch(d1c_grad12_kernel<9>, grid, dim3(256 * kD1cTeams), p.ldsd, s, X, A1, D2, P.W2, slab12, g,
                                    d1c_xs_floats(h), p.d1c_parts)
                           : launch(d1_grad12_kernel<N1, N2, F1>, grid, blk, 0, s, X, A1, D2, P.W2, slab12, g))
