@@ -39,6 +39,9 @@ inline uint32_t grid_for(size_t total, uint32_t block, uint32_t cap = 1u << 20) 
   return g > cap ? cap : static_cast<uint32_t>(g);
 }
 
+// the 256-byte units every workspace region is carved in
+inline size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
+
 // kernel-path selection (srcnn_set_path): 0 auto, 1 generic only
 extern int g_path;
 // matrix-core arithmetic (srcnn_set_arith): 0 split bf16, 1 fp32 MFMA only

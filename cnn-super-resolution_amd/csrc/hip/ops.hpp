@@ -1,5 +1,6 @@
 // ops.hpp -- internal launchers behind srcnn.h (no validation here; abi.cpp
-// validates shapes exactly once, then dispatches generic vs gfx950 paths).
+// validates shapes exactly once, then dispatches generic vs gfx950 paths, and
+// abi_upscale.cpp validates and launches the image-level operators).
 // The net-level families answer "is this shape served, and what does it
 // need" through their *_plan queries, which take no buffer.
 #pragma once

@@ -225,33 +225,77 @@ Event ConfigBasedDataPipeline::forward(LayerAllocationPool& l1, LayerAllocationP
                        _out_3_gpu_buf, &e2);
 }
 
-void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, ImageData& result) {
-  check_initialized(LOAD_KERNEL_LAYERS);
-  require(scale >= 1 && scale <= 4, "super_resolve: scale must be 1, 2, 3 or 4");
-  require(low_res.w > 0 && low_res.h > 0, "super_resolve: empty image");
+// super_resolve (`who`) and super_resolve_to: the image through one ABI call
+// (`abi`: srcnn_<abi>, counted under that name) to out_w x out_h
+template <typename Query, typename Call>
+void ConfigBasedDataPipeline::upscale_image(const std::string& who, const char* abi, Kernel*& kernel,
+                                            ImageData& low_res, size_t out_w, size_t out_h, Query query,
+                                            Call call, ImageData& result) {
+  require(low_res.w > 0 && low_res.h > 0, who + ": empty image");
   GpuAllocationPool own;  // the pipeline's flat parameters
-  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve needs the pipeline's flat parameters");
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), who + " needs the pipeline's flat parameters");
   srcnn_net nt = net();
-  const size_t W = size_t(low_res.w) * scale, H = size_t(low_res.h) * scale;
-  const size_t ws = srcnn_upscale_workspace_bytes(&nt, low_res.w, low_res.h, scale);
-  require(ws > 0, std::string("super_resolve: ") + srcnn_last_error());
+  const size_t ws = query(&nt);
+  require(ws > 0, who + ": " + srcnn_last_error());
   MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, low_res.w, low_res.h);
   _context->write_image(rgba, low_res, true);
-  MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, W * H * 3);
+  MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, out_w * out_h * 3);
   void* wsp = scratch(ws);
-  if (!_upscale_kernel)
-    _upscale_kernel = _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale", 0, 0, 0, false, net_defines());
+  if (!kernel)
+    kernel = _context->create_kernel(srcnn::KernelKind::Net, std::string("srcnn_") + abi, 0, 0, 0, false, net_defines());
   {
-    srcnn::Context::Launch l(*_context, *_upscale_kernel);
-    check(srcnn_upscale(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), low_res.w, low_res.h, scale,
-                        _context->fptr(_flat_params), static_cast<uint8_t*>(_context->ptr(rgb)), wsp, ws,
-                        _context->stream()),
-          "upscale");
+    srcnn::Context::Launch l(*_context, *kernel);
+    check(call(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), _context->fptr(_flat_params),
+               static_cast<uint8_t*>(_context->ptr(rgb)), wsp, ws, _context->stream()),
+          abi);
   }
-  result = ImageData(int(W), int(H), 3);
+  result = ImageData(int(out_w), int(out_h), 3);
   _context->read_buffer(rgb, 0, result.data.size(), result.data.data(), true);
   _context->raw_memory(rgb)->release();
   _context->raw_memory(rgba)->release();
+}
+
+void ConfigBasedDataPipeline::super_resolve(ImageData& low_res, unsigned scale, ImageData& result) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  require(scale >= 1 && scale <= 4, "super_resolve: scale must be 1, 2, 3 or 4");
+  const unsigned w = low_res.w, h = low_res.h;
+  upscale_image(
+      "super_resolve", "upscale", _upscale_kernel, low_res, size_t(w) * scale, size_t(h) * scale,
+      [&](const srcnn_net* nt) { return srcnn_upscale_workspace_bytes(nt, w, h, scale); },
+      [&](const srcnn_net* nt, const uint8_t* rgba, const float* params, uint8_t* rgb, void* ws, size_t ws_bytes,
+          srcnn_stream_t s) { return srcnn_upscale(nt, rgba, w, h, scale, params, rgb, ws, ws_bytes, s); },
+      result);
+}
+
+void ConfigBasedDataPipeline::super_resolve_to(ImageData& low_res, unsigned out_w, unsigned out_h,
+                                               ImageData& result) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  const unsigned w = low_res.w, h = low_res.h;
+  upscale_image(
+      "super_resolve_to", "upscale_to", _upscale_to_kernel, low_res, out_w, out_h,
+      [&](const srcnn_net* nt) { return srcnn_upscale_to_workspace_bytes(nt, w, h, out_w, out_h); },
+      [&](const srcnn_net* nt, const uint8_t* rgba, const float* params, uint8_t* rgb, void* ws, size_t ws_bytes,
+          srcnn_stream_t s) { return srcnn_upscale_to(nt, rgba, w, h, out_w, out_h, params, rgb, ws, ws_bytes, s); },
+      result);
+}
+
+// super_resolve_frame (`who`) and super_resolve_frame_to: one ABI call on the
+// caller's stream, or on the context's and counted as kernel srcnn_<abi>
+template <typename Call>
+void ConfigBasedDataPipeline::upscale_frame(const std::string& who, const char* abi, Kernel*& kernel,
+                                            srcnn_stream_t stream, Call call) {
+  check_initialized(LOAD_KERNEL_LAYERS);
+  GpuAllocationPool own;  // the pipeline's flat parameters
+  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), who + " needs the pipeline's flat parameters");
+  srcnn_net nt = net();
+  if (stream) {
+    check(call(&nt, _context->fptr(_flat_params), stream), abi);
+    return;
+  }
+  if (!kernel)
+    kernel = _context->create_kernel(srcnn::KernelKind::Net, std::string("srcnn_") + abi, 0, 0, 0, false, net_defines());
+  srcnn::Context::Launch l(*_context, *kernel);
+  check(call(&nt, _context->fptr(_flat_params), _context->stream()), abi);
 }
 
 size_t ConfigBasedDataPipeline::super_resolve_yuv_workspace_bytes(unsigned w, unsigned h, unsigned scale) {
@@ -269,57 +313,16 @@ void ConfigBasedDataPipeline::super_resolve_yuv(const srcnn_yuv_frame& src, cons
 void ConfigBasedDataPipeline::super_resolve_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src,
                                                   const srcnn_yuv_frame& dst, unsigned w, unsigned h, unsigned scale,
                                                   void* ws, size_t ws_bytes, srcnn_stream_t stream) {
-  check_initialized(LOAD_KERNEL_LAYERS);
-  GpuAllocationPool own;  // the pipeline's flat parameters
-  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_frame needs the pipeline's flat parameters");
-  srcnn_net nt = net();
-  if (stream) {
-    check(srcnn_upscale_frame(&nt, &fmt, &src, &dst, w, h, scale, _context->fptr(_flat_params), ws, ws_bytes, stream),
-          "upscale_frame");
-    return;
-  }
-  if (!_upscale_frame_kernel)
-    _upscale_frame_kernel =
-        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame", 0, 0, 0, false, net_defines());
-  srcnn::Context::Launch l(*_context, *_upscale_frame_kernel);
-  check(srcnn_upscale_frame(&nt, &fmt, &src, &dst, w, h, scale, _context->fptr(_flat_params), ws, ws_bytes,
-                            _context->stream()),
-        "upscale_frame");
+  upscale_frame("super_resolve_frame", "upscale_frame", _upscale_frame_kernel, stream,
+                [&](const srcnn_net* nt, const float* params, srcnn_stream_t s) {
+                  return srcnn_upscale_frame(nt, &fmt, &src, &dst, w, h, scale, params, ws, ws_bytes, s);
+                });
 }
 
 size_t ConfigBasedDataPipeline::super_resolve_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w,
                                                                  unsigned out_h) {
   srcnn_net nt = net();
   return srcnn_upscale_to_workspace_bytes(&nt, w, h, out_w, out_h);
-}
-
-void ConfigBasedDataPipeline::super_resolve_to(ImageData& low_res, unsigned out_w, unsigned out_h,
-                                               ImageData& result) {
-  check_initialized(LOAD_KERNEL_LAYERS);
-  require(low_res.w > 0 && low_res.h > 0, "super_resolve_to: empty image");
-  GpuAllocationPool own;  // the pipeline's flat parameters
-  require(bind_flat(own.layer_1, own.layer_2, own.layer_3), "super_resolve_to needs the pipeline's flat parameters");
-  srcnn_net nt = net();
-  const size_t ws = srcnn_upscale_to_workspace_bytes(&nt, low_res.w, low_res.h, out_w, out_h);
-  require(ws > 0, std::string("super_resolve_to: ") + srcnn_last_error());
-  MemoryHandle rgba = _context->create_image(srcnn::MEM_READ_WRITE, low_res.w, low_res.h);
-  _context->write_image(rgba, low_res, true);
-  MemoryHandle rgb = _context->allocate(srcnn::MEM_READ_WRITE, size_t(out_w) * out_h * 3);
-  void* wsp = scratch(ws);
-  if (!_upscale_to_kernel)
-    _upscale_to_kernel =
-        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_to", 0, 0, 0, false, net_defines());
-  {
-    srcnn::Context::Launch l(*_context, *_upscale_to_kernel);
-    check(srcnn_upscale_to(&nt, static_cast<const uint8_t*>(_context->ptr(rgba)), low_res.w, low_res.h, out_w, out_h,
-                           _context->fptr(_flat_params), static_cast<uint8_t*>(_context->ptr(rgb)), wsp, ws,
-                           _context->stream()),
-          "upscale_to");
-  }
-  result = ImageData(int(out_w), int(out_h), 3);
-  _context->read_buffer(rgb, 0, result.data.size(), result.data.data(), true);
-  _context->raw_memory(rgb)->release();
-  _context->raw_memory(rgba)->release();
 }
 
 size_t ConfigBasedDataPipeline::super_resolve_frame_to_workspace_bytes(unsigned w, unsigned h, unsigned out_w,
@@ -332,24 +335,10 @@ void ConfigBasedDataPipeline::super_resolve_frame_to(const srcnn_yuv_format& fmt
                                                      const srcnn_yuv_frame& dst, unsigned w, unsigned h,
                                                      unsigned out_w, unsigned out_h, void* ws, size_t ws_bytes,
                                                      srcnn_stream_t stream) {
-  check_initialized(LOAD_KERNEL_LAYERS);
-  GpuAllocationPool own;  // the pipeline's flat parameters
-  require(bind_flat(own.layer_1, own.layer_2, own.layer_3),
-          "super_resolve_frame_to needs the pipeline's flat parameters");
-  srcnn_net nt = net();
-  if (stream) {
-    check(srcnn_upscale_frame_to(&nt, &fmt, &src, &dst, w, h, out_w, out_h, _context->fptr(_flat_params), ws,
-                                 ws_bytes, stream),
-          "upscale_frame_to");
-    return;
-  }
-  if (!_upscale_frame_to_kernel)
-    _upscale_frame_to_kernel =
-        _context->create_kernel(srcnn::KernelKind::Net, "srcnn_upscale_frame_to", 0, 0, 0, false, net_defines());
-  srcnn::Context::Launch l(*_context, *_upscale_frame_to_kernel);
-  check(srcnn_upscale_frame_to(&nt, &fmt, &src, &dst, w, h, out_w, out_h, _context->fptr(_flat_params), ws, ws_bytes,
-                               _context->stream()),
-        "upscale_frame_to");
+  upscale_frame("super_resolve_frame_to", "upscale_frame_to", _upscale_frame_to_kernel, stream,
+                [&](const srcnn_net* nt, const float* params, srcnn_stream_t s) {
+                  return srcnn_upscale_frame_to(nt, &fmt, &src, &dst, w, h, out_w, out_h, params, ws, ws_bytes, s);
+                });
 }
 
 bool ConfigBasedDataPipeline::evaluate(ImageData& truth, unsigned scale, unsigned shave, QualityReport& q_net,

@@ -225,6 +225,13 @@ class ConfigBasedDataPipeline : public DataPipeline {
   /** one chunk of n samples of w x h already in the batch buffers: forward +
    * (backprop ? gradient accumulation : squared error, which is returned) */
   float run_chunk(bool backprop, bool flat, GpuAllocationPool&, size_t w, size_t h, size_t n);
+  /** what super_resolve / super_resolve_to and super_resolve_frame /
+   * super_resolve_frame_to share: `who` in their errors, the ABI call srcnn_<abi> */
+  template <typename Query, typename Call>
+  void upscale_image(const std::string& who, const char* abi, Kernel*& kernel, ImageData& low_res, size_t out_w,
+                     size_t out_h, Query query, Call call, ImageData& result);
+  template <typename Call>
+  void upscale_frame(const std::string& who, const char* abi, Kernel*& kernel, srcnn_stream_t stream, Call call);
   void fill_random_parameters(LayerData&, ParametersDistribution&, uint64_t seed);
   size_t load_parameters_file(const char* file);
 
