@@ -3,7 +3,7 @@
 // upscale of an image or a Y'CbCr frame through the net by a scale or to any
 // size (srcnn_upscale, _yuv, _frame, _to, _frame_to), and what prepares and
 // judges images around them (srcnn_downscale_rgba, srcnn_gather_*,
-// srcnn_make_pairs, srcnn_quality, srcnn_evaluate).
+// srcnn_make_pairs, srcnn_quality, srcnn_quality_frame, srcnn_evaluate).
 //
 // Every call validates its arguments before its first launch.  The net-level
 // calls are composed of the public operators and of srcnn_sub_mean and
@@ -484,6 +484,74 @@ int quality_image(const char* who, const void* p, int fmt, uint32_t pitch, uint3
 }
 size_t pixel_bytes(int fmt) { return fmt == SRCNN_PIX_RGB8 ? 3 : 4; }
 
+// srcnn_quality_frame: the shaved luma window Ws x Hs of a w x h frame and the
+// chroma windows CWs x CHs that sx columns and sy rows per side leave of its
+// cw x ch chroma planes, against the SSIM window and the
+// kernels' int coordinates
+bool known_subsampling(uint32_t cx, uint32_t cy) {
+  return (cx == 2 && cy == 2) || (cx == 2 && cy == 1) || (cx == 1 && cy == 1);
+}
+struct FrameQualityDims {
+  uint32_t Ws, Hs, cw, ch, sx, sy, CWs, CHs;
+  size_t ws_bytes;  // two words per luma tile, one per chroma tile and plane
+};
+int quality_frame_dims(const char* who, uint32_t w, uint32_t h, uint32_t cx, uint32_t cy, uint32_t shave,
+                       FrameQualityDims* d) {
+  SRCNN_REQUIRE(known_subsampling(cx, cy),
+                "%s: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)", who, cx, cy);
+  SRCNN_REQUIRE(2 * (uint64_t)shave + 11 <= w && 2 * (uint64_t)shave + 11 <= h,
+                "%s: frame %ux%u with %u pixels shaved per side is smaller than the 11x11 window", who, w, h,
+                shave);
+  SRCNN_REQUIRE((uint64_t)w * h <= kIndexMax,
+                "%s: %ux%u exceeds the kernels' 32-bit index: a plane's samples must number at most 2^31-1",
+                who, w, h);
+  d->Ws = w - 2 * shave;
+  d->Hs = h - 2 * shave;
+  d->cw = (w - 1) / cx + 1;
+  d->ch = (h - 1) / cy + 1;
+  d->sx = (shave + cx - 1) / cx;
+  d->sy = (shave + cy - 1) / cy;
+  SRCNN_REQUIRE(2 * (uint64_t)d->sx < d->cw && 2 * (uint64_t)d->sy < d->ch,
+                "%s: %u pixels shaved per side leave nothing of the %ux%u chroma planes", who, shave, d->cw,
+                d->ch);
+  d->CWs = d->cw - 2 * d->sx;
+  d->CHs = d->ch - 2 * d->sy;
+  d->ws_bytes = align_up(((size_t)srcnn::quality_tile_count(d->Ws, d->Hs) +
+                          (size_t)srcnn::quality_chroma_tile_count(d->CWs, d->CHs)) *
+                         2 * sizeof(double));
+  return SRCNN_OK;
+}
+// one frame of srcnn_quality_frame with its format, as srcnn_upscale_frame
+// checks a frame; *side: its shaved windows
+int quality_frame_side(const char* who, const srcnn_yuv_format* fmt, const srcnn_yuv_frame* f, uint32_t w,
+                       uint32_t h, const FrameQualityDims& d, uint32_t shave, srcnn::QualityFrameSide* side) {
+  uint32_t B;
+  if (int rc = yuv_range(who, fmt->range)) return rc;
+  if (int rc = yuv_samples(who, fmt->bits, fmt->msb, &B)) return rc;
+  if (int rc = yuv_layout(who, fmt->layout)) return rc;
+  const bool semi = fmt->layout == SRCNN_YUV_SEMIPLANAR;
+  const uint32_t nch = semi ? 2 : 1;
+  SRCNN_REQUIRE(f->y && f->u, "%s: null plane", who);
+  if (semi) {
+    SRCNN_REQUIRE(!f->v, "%s: a semi-planar frame has no v plane", who);
+  } else {
+    SRCNN_REQUIRE(f->v, "%s: null plane", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, f->y) && !odd_address(B, f->u) && !odd_address(B, f->v),
+                "%s: odd address of two-byte samples", who);
+  if (int rc = plane_dims(who, w, h, f->pitch_y, B)) return rc;
+  if (int rc = plane_dims(who, d.cw, d.ch, f->pitch_c, B, nch)) return rc;
+  const size_t oc = (size_t)d.sy * f->pitch_c + (size_t)d.sx * nch * B;
+  *side = srcnn::QualityFrameSide{f->y + (size_t)shave * f->pitch_y + (size_t)shave * B,
+                                  f->u + oc,
+                                  semi ? nullptr : f->v + oc,
+                                  f->pitch_y,
+                                  f->pitch_c,
+                                  fmt->msb != 0,
+                                  semi};
+  return SRCNN_OK;
+}
+
 // regions of the evaluate workspace: low-resolution image | rgb [Hc][Wc][3] |
 // luma plane [Hc][Wc] | srcnn_upscale's workspace | srcnn_quality's, each
 // 256-byte aligned
@@ -702,6 +770,36 @@ int srcnn_quality(const void* a, int fmt_a, uint32_t pitch_a, const void* b, int
   const char* pb = static_cast<const char*>(b) + ((size_t)shave * pitch_b + shave) * pixel_bytes(fmt_b);
   return srcnn::quality(pa, fmt_a, pitch_a, pb, fmt_b, pitch_b, d.Ws, d.Hs, result,
                         static_cast<double*>(ws), as_stream(stream));
+}
+
+size_t srcnn_quality_frame_workspace_bytes(uint32_t w, uint32_t h, uint32_t cx, uint32_t cy,
+                                           uint32_t shave) {
+  FrameQualityDims d;
+  return quality_frame_dims("quality_frame", w, h, cx, cy, shave, &d) ? 0 : d.ws_bytes;
+}
+
+int srcnn_quality_frame(const srcnn_yuv_format* fmt_a, const srcnn_yuv_frame* a,
+                        const srcnn_yuv_format* fmt_b, const srcnn_yuv_frame* b, uint32_t w, uint32_t h,
+                        uint32_t shave, double* result, void* ws, size_t ws_bytes,
+                        srcnn_stream_t stream) {
+  const char* who = "quality_frame";
+  SRCNN_REQUIRE(fmt_a && fmt_b, "%s: null srcnn_yuv_format", who);
+  SRCNN_REQUIRE(a && b && result && ws, "%s: null buffer", who);
+  FrameQualityDims d;
+  if (int rc = quality_frame_dims(who, w, h, fmt_a->cx, fmt_a->cy, shave, &d)) return rc;
+  SRCNN_REQUIRE(fmt_a->bits == fmt_b->bits && fmt_a->cx == fmt_b->cx && fmt_a->cy == fmt_b->cy &&
+                    fmt_a->range == fmt_b->range,
+                "%s: the formats differ in bits (%u / %u), subsampling (%ux%u / %ux%u) or range (%d / %d)",
+                who, fmt_a->bits, fmt_b->bits, fmt_a->cx, fmt_a->cy, fmt_b->cx, fmt_b->cy, fmt_a->range,
+                fmt_b->range);
+  srcnn::QualityFrameSide sa, sb;
+  if (int rc = quality_frame_side(who, fmt_a, a, w, h, d, shave, &sa)) return rc;
+  if (int rc = quality_frame_side(who, fmt_b, b, w, h, d, shave, &sb)) return rc;
+  SRCNN_REQUIRE((((uintptr_t)result | (uintptr_t)ws) & 7) == 0,
+                "%s: result and workspace hold 8-byte words and must be 8-byte aligned", who);
+  if (ws_bytes < d.ws_bytes)
+    return fail(SRCNN_ERR_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, d.ws_bytes);
+  return srcnn::quality_frame(sa, sb, fmt_a->bits, d.Ws, d.Hs, d.CWs, d.CHs, result, ws, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------

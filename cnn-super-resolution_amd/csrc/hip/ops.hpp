@@ -311,6 +311,20 @@ int preload_pairs();
 uint64_t quality_tile_count(uint32_t Ws, uint32_t Hs);
 int quality(const void* a, int fmt_a, uint32_t pitch_a, const void* b, int fmt_b, uint32_t pitch_b,
             uint32_t Ws, uint32_t Hs, double* result, double* partial, hipStream_t s);
+// the same of two Y'CbCr frames: PSNR per plane, SSIM on luma
+// into result [8].  A side's pointers are the first samples of its shaved
+// windows, Ws x Hs of luma and CWs x CHs of each chroma plane; pitches in
+// bytes; semiplanar: c0 holds the (U, V) pairs, c1 unused.  ws: two 8-byte
+// words per luma tile, then one per chroma tile (quality_chroma_tile_count)
+// and plane.  Three launches.
+struct QualityFrameSide {
+  const void *y, *c0, *c1;
+  uint32_t pitch_y, pitch_c;
+  bool msb, semiplanar;
+};
+uint64_t quality_chroma_tile_count(uint32_t CWs, uint32_t CHs);
+int quality_frame(const QualityFrameSide& a, const QualityFrameSide& b, uint32_t bits, uint32_t Ws,
+                  uint32_t Hs, uint32_t CWs, uint32_t CHs, double* result, void* ws, hipStream_t s);
 int preload_quality();
 
 }  // namespace srcnn

@@ -426,6 +426,35 @@ QualityReport DataPipeline::quality(ImageData& img, ImageData& ref, unsigned sha
   return q;
 }
 
+void DataPipeline::quality_frame(const srcnn_yuv_format& fmt_a, const srcnn_yuv_frame& a,
+                                 const srcnn_yuv_format& fmt_b, const srcnn_yuv_frame& b, unsigned w, unsigned h,
+                                 unsigned shave, double* result, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  if (stream) {
+    check(srcnn_quality_frame(&fmt_a, &a, &fmt_b, &b, w, h, shave, result, ws, ws_bytes, stream), "quality_frame");
+    return;
+  }
+  if (!_quality_frame_kernel)
+    _quality_frame_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_quality_frame");
+  srcnn::Context::Launch l(*_context, *_quality_frame_kernel);
+  check(srcnn_quality_frame(&fmt_a, &a, &fmt_b, &b, w, h, shave, result, ws, ws_bytes, _context->stream()),
+        "quality_frame");
+}
+
+FrameQualityReport DataPipeline::quality_frame(const srcnn_yuv_format& fmt_a, const srcnn_yuv_frame& a,
+                                               const srcnn_yuv_format& fmt_b, const srcnn_yuv_frame& b, unsigned w,
+                                               unsigned h, unsigned shave) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  const size_t ws = srcnn_quality_frame_workspace_bytes(w, h, fmt_a.cx, fmt_a.cy, shave);
+  require(ws > 0, std::string("quality_frame: ") + srcnn_last_error());
+  MemoryHandle res = _context->allocate(srcnn::MEM_READ_WRITE, 8 * sizeof(double));
+  quality_frame(fmt_a, a, fmt_b, b, w, h, shave, static_cast<double*>(_context->ptr(res)), scratch(ws), ws, nullptr);
+  double r[8];
+  _context->read_buffer(res, 0, sizeof(r), r, true);
+  _context->raw_memory(res)->release();
+  return FrameQualityReport{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+}
+
 Event DataPipeline::gather_tiles(MemoryHandle plane, size_t pw, size_t ph, size_t x0, size_t y0,
                                  size_t stride, size_t nx, size_t ny, size_t tw, size_t th,
                                  bool sub_mean, MemoryHandle& tiles, MemoryHandle* means, Event* ev) {

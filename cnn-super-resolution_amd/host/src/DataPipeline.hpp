@@ -36,6 +36,13 @@ struct QualityReport {
   double mse = 0, psnr = 0, ssim = 0;
 };
 
+/** srcnn_quality_frame's eight results: the mean squared
+ * error of the integer code values and its PSNR per plane, the luma's SSIM,
+ * and the PSNR over all three planes (+inf for identical planes). */
+struct FrameQualityReport {
+  double mse_y = 0, psnr_y = 0, ssim_y = 0, mse_u = 0, psnr_u = 0, mse_v = 0, psnr_v = 0, psnr_all = 0;
+};
+
 class DataPipeline {
  public:
   static int LOAD_KERNEL_LUMA;
@@ -129,6 +136,20 @@ class DataPipeline {
    * 3 or 4 channels each), measured on the device on the full-range luma
    * with `shave` pixels dropped per side (srcnn_quality).  Blocking. */
   QualityReport quality(ImageData& img, ImageData& ref, unsigned shave);
+
+  /** Extension, Y'CbCr frames: PSNR per plane and SSIM on luma
+   * of the device frames `a` and `b` of w x h luma samples, each with its own
+   * format (equal bits, subsampling and range), `shave` luma pixels dropped
+   * per side (srcnn_quality_frame).  Blocking. */
+  FrameQualityReport quality_frame(const srcnn_yuv_format& fmt_a, const srcnn_yuv_frame& a,
+                                   const srcnn_yuv_format& fmt_b, const srcnn_yuv_frame& b, unsigned w, unsigned h,
+                                   unsigned shave);
+  /** The same, enqueued: the eight doubles go to `result` (device) through the
+   * caller's workspace (srcnn_quality_frame_workspace_bytes), on `stream`, or,
+   * with no stream, on the context's, where the call is counted and timed. */
+  void quality_frame(const srcnn_yuv_format& fmt_a, const srcnn_yuv_frame& a, const srcnn_yuv_format& fmt_b,
+                     const srcnn_yuv_frame& b, unsigned w, unsigned h, unsigned shave, double* result, void* ws,
+                     size_t ws_bytes, srcnn_stream_t stream);
 
   /** Extension: cut nx x ny tiles of tw x th floats, tile (ix, iy) from
    * (x0 + ix*stride, y0 + iy*stride), out of the plane_w x plane_h float plane
@@ -229,6 +250,7 @@ class DataPipeline {
   Kernel* _gather_tiles_kernel = nullptr;
   Kernel* _gather_batch_kernel = nullptr;
   Kernel* _quality_kernel = nullptr;
+  Kernel* _quality_frame_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;
   Kernel* _sum_squared_kernel = nullptr;

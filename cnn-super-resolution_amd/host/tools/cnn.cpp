@@ -41,10 +41,24 @@
 //           size (RGB), resampled on the device by the inverse of the upscale
 //           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
 //           for `cnn upscale`.  Needs no CONFIG.
+//           --ref TRUTH.y4m (Y4M input only): TRUTH has the output's size,
+//           subsampling and depth; each of its frames is uploaded into the
+//           slot and the upscaled frame is measured against it where it lies,
+//           on the device (srcnn_quality_frame on the slot's stream), --shave
+//           pixels dropped per side (default --scale; 0 with --size).  Prints
+//           what `cnn quality` prints for OUT against TRUTH; -o is optional.
 // quality:  (extension) IN and --ref REF are two image files of equal size; prints
 //           the PSNR, SSIM and MSE of IN against REF, measured on the device
 //           on the full-range luma (srcnn_quality), --shave pixels dropped per
 //           side (default 0).  Needs no CONFIG and no OUT.
+//           If IN starts with the YUV4MPEG2 magic, IN and REF are Y4M videos
+//           of equal size, subsampling and depth: the frames stream through
+//           two slots and each pair is measured on the code values
+//           (srcnn_quality_frame): one line per frame with the
+//           PSNR of Y, U, V and of all three and the luma's SSIM, then the
+//           stream's numbers: the PSNR of the mean of the frames' mse per
+//           plane, the mean SSIM, and the lowest psnr y with its frame.
+//           --frames N stops after N pairs; -o writes the numbers as JSON.
 // evaluate: (extension) IN is a full-size image or a directory of them; each
 //           is downscaled by S, upscaled again by the net and by plain bicubic
 //           on the device and both results are measured against the image
@@ -125,13 +139,13 @@ struct Args {
   bool augment = false;         // ... with a random orientation per training sample and epoch
   bool random_origins = false;  // ... with a random crop per training sample and epoch
   std::string config, in, out;
-  std::string ref;       // quality: --ref
-  size_t frames = 0;     // upscale, Y4M: --frames (0: all)
+  std::string ref;       // quality: --ref; upscale, Y4M: the truth to measure against
+  size_t frames = 0;     // upscale, quality, Y4M: --frames (0: all)
   bool frames_set = false;
   int range = -1;        // upscale, Y4M: --range (-1: the header's, 0 limited, 1 full)
   unsigned slots = 2;    // upscale, Y4M: --slots
   bool slots_set = false;
-  unsigned shave = 0;    // quality, evaluate: --shave (evaluate: default --scale)
+  unsigned shave = 0;    // quality, evaluate, upscale --ref: --shave (evaluate, upscale --scale: default --scale)
   bool shave_set = false;
   size_t epochs = 0;
   uint64_t seed = 0;
@@ -170,6 +184,10 @@ void usage() {
          "  quality               quality mode: PSNR, SSIM and MSE of the image IN against\n"
          "                        --ref REF (equal sizes), measured on the device on the\n"
          "                        full-range luma; -c and -o are not needed\n"
+         "                        Two Y4M videos (equal size, subsampling and depth) are\n"
+         "                        measured frame by frame on their code values: PSNR of Y,\n"
+         "                        U, V and of all three, SSIM of Y, then the stream's\n"
+         "                        numbers; -o writes them as JSON\n"
          "  evaluate              evaluate mode: IN is a full-size image or a directory of\n"
          "                        them; each is downscaled by --scale, upscaled again by the\n"
          "                        net and by plain bicubic, and both are measured against\n"
@@ -188,13 +206,17 @@ void usage() {
          "  --size WxH            upscale: the output size instead of --scale, each axis\n"
          "                        within 1x .. 4x of the input's (any ratio, also a\n"
          "                        different one per axis)\n"
-         "  --frames N            upscale, Y4M: stop after N frames\n"
+         "  --frames N            upscale, quality, Y4M: stop after N frames\n"
          "  --range full|limited  upscale, Y4M: the luma range (default: the header's\n"
          "                        XCOLORRANGE, else limited)\n"
          "  --slots N             upscale, Y4M: frames in flight, 1 or 2 (default 2)\n"
-         "  --ref REF             quality: the image IN is measured against\n"
-         "  --shave N             quality, evaluate: pixels dropped on every side before\n"
-         "                        measuring (default: 0 for quality, --scale for evaluate)\n"
+         "  --ref REF             quality: the image or Y4M video IN is measured against\n"
+         "                        upscale, Y4M: the Y4M video of the output's size every\n"
+         "                        upscaled frame is measured against on the device; prints\n"
+         "                        what quality prints (-o is then optional)\n"
+         "  --shave N             quality, evaluate, upscale --ref: pixels dropped on every\n"
+         "                        side before measuring (default: 0 for quality, --scale\n"
+         "                        for evaluate and upscale --scale, 0 for upscale --size)\n"
          "  --from-images         train: IN is a directory of full-size images; the sample\n"
          "                        pairs are cut on the device, the inputs degraded by\n"
          "                        --scale as the upscale mode resamples\n"
@@ -217,6 +239,13 @@ void usage() {
          "  --mini-batches M      mini-batches per epoch (default 2)\n"
          "  --save-momentum       also store the momentum in the parameters file; a file\n"
          "                        that holds it resumes training with it (extension)\n";
+}
+
+/** whether the file starts with the YUV4MPEG2 magic (false if it cannot be read) */
+bool is_y4m(const std::string& path) {
+  std::ifstream in(path, std::ios::binary);
+  char magic[9] = {};
+  return in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0;
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -342,12 +371,17 @@ bool parse(int argc, char** argv, Args& a) {
         "--scale needs the upscale mode, the downscale mode, the evaluate mode or train --from-images");
   if (a.size_set && a.scale_set) throw std::runtime_error("--size and --scale exclude each other");
   if (a.size_set && !a.upscale) throw std::runtime_error("--size needs the upscale mode");
-  if ((a.frames_set || a.range >= 0 || a.slots_set) && !a.upscale)
-    throw std::runtime_error("--frames, --range and --slots need the upscale mode");
-  if (!a.ref.empty() && !a.quality) throw std::runtime_error("--ref needs the quality mode");
-  if (a.shave_set && !a.quality && !a.evaluate)
-    throw std::runtime_error("--shave needs the quality mode or the evaluate mode");
-  if (a.evaluate && !a.shave_set) a.shave = a.scale;  // the literature's rule
+  if ((a.range >= 0 || a.slots_set) && !a.upscale)
+    throw std::runtime_error("--range and --slots need the upscale mode");
+  if (a.frames_set && !a.upscale && !a.quality)
+    throw std::runtime_error("--frames needs the upscale mode or the quality mode");
+  // (upscale --ref measures a Y4M stream's frames; an image input has nothing to measure per frame)
+  if (!a.ref.empty() && !a.quality && !(a.upscale && is_y4m(a.in)))
+    throw std::runtime_error("--ref needs the quality mode, or the upscale mode with a Y4M input");
+  if (a.shave_set && !a.quality && !a.evaluate && !(a.upscale && !a.ref.empty()))
+    throw std::runtime_error("--shave needs the quality mode or the evaluate mode (or upscale --ref)");
+  if ((a.evaluate || (a.upscale && !a.ref.empty() && !a.size_set)) && !a.shave_set)
+    a.shave = a.scale;  // the literature's rule
   if (a.quality) {
     if (a.in.empty() || a.ref.empty()) throw std::runtime_error("--in and --ref are required");
   } else if (a.downscale) {
@@ -445,6 +479,9 @@ struct FrameSlot {
   void *dev_in = nullptr, *dev_out = nullptr, *ws = nullptr;
   srcnn_yuv_frame src{}, dst{};
   bool busy = false;  // a frame is enqueued and not yet written
+  // --ref: the truth frame, the metric's workspace and its 8 doubles (device, and a pinned copy)
+  void *host_ref = nullptr, *dev_ref = nullptr, *qws = nullptr, *dev_res = nullptr, *host_res = nullptr;
+  srcnn_yuv_frame ref{};
 
   FrameSlot() = default;
   FrameSlot(const FrameSlot&) = delete;
@@ -454,8 +491,13 @@ struct FrameSlot {
     srcnn_free(dev_in);
     srcnn_free(dev_out);
     srcnn_free(ws);
+    srcnn_free(dev_ref);
+    srcnn_free(qws);
+    srcnn_free(dev_res);
     srcnn_host_free(host_in);
     srcnn_host_free(host_out);
+    srcnn_host_free(host_ref);
+    srcnn_host_free(host_res);
     if (stream) srcnn_stream_destroy(stream);
   }
   static srcnn_yuv_frame planes(void* base, const srcnn::y4m::Header& hd) {
@@ -473,7 +515,129 @@ struct FrameSlot {
     src = planes(dev_in, in);
     dst = planes(dev_out, out);
   }
+  /** the buffers of --ref: a truth frame of `out`'s geometry and the metric's */
+  void init_ref(const srcnn::y4m::Header& out, size_t qws_bytes) {
+    srcnn::check(srcnn_host_alloc(&host_ref, out.frame_bytes()), "host_alloc");
+    srcnn::check(srcnn_host_alloc(&host_res, 8 * sizeof(double)), "host_alloc");
+    srcnn::check(srcnn_malloc(&dev_ref, out.frame_bytes()), "malloc");
+    srcnn::check(srcnn_malloc(&qws, qws_bytes), "malloc");
+    srcnn::check(srcnn_malloc(&dev_res, 8 * sizeof(double)), "malloc");
+    ref = planes(dev_ref, out);
+  }
 };
+
+/** doubles as the reports print them: 17 significant digits, so that a reader
+ * gets the device's value back bit for bit; "inf" for identical images */
+std::string num(double v) {
+  if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+  char buf[40];
+  std::snprintf(buf, sizeof(buf), "%.17g", v);
+  return buf;
+}
+/** the same for the JSON report, which has no infinity: null */
+std::string json_num(double v) { return std::isfinite(v) ? num(v) : "null"; }
+
+/** The frames' srcnn_quality_frame results of one stream (`cnn quality` on two
+ * Y4M files, `cnn upscale --ref`): one line per frame as it arrives, then the
+ * stream's numbers.  A frame's mse over all planes is the
+ * planes' mse weighted by their sample counts. */
+class StreamQuality {
+ public:
+  StreamQuality(const srcnn::y4m::Header& hd, unsigned shave) : _hd(hd), _shave(shave) {
+    const uint64_t sx = (shave + hd.cx - 1) / hd.cx, sy = (shave + hd.cy - 1) / hd.cy;
+    _ny = double((hd.w - 2 * uint64_t(shave)) * (hd.h - 2 * uint64_t(shave)));
+    _nc = double((hd.cw() - 2 * sx) * (hd.ch() - 2 * sy));
+    _peak2 = double((1u << hd.bits) - 1) * double((1u << hd.bits) - 1);
+  }
+  /** the call's own complaint about sizes too small for the metric, before any frame */
+  static void check(const srcnn::y4m::Header& hd, unsigned shave) {
+    const size_t ws = srcnn_quality_frame_workspace_bytes(hd.w, hd.h, hd.cx, hd.cy, shave);
+    srcnn::require(ws > 0, std::string("quality: ") + srcnn_last_error());
+  }
+  void add(const double* r) {
+    const FrameQualityReport q{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+    std::cout << "frame " << _frames.size() << ": psnr y " << num(q.psnr_y) << " dB u " << num(q.psnr_u) << " dB v "
+              << num(q.psnr_v) << " dB all " << num(q.psnr_all) << " dB ssim " << num(q.ssim_y) << std::endl;
+    _frames.push_back(q);
+  }
+  size_t count() const { return _frames.size(); }
+  struct Totals {
+    double mse_y = 0, mse_u = 0, mse_v = 0, mse_all = 0, ssim = 0, min_psnr_y = INFINITY;
+    size_t min_frame = 0;
+  };
+  Totals totals() const {
+    Totals t;
+    const double n = double(_frames.size());
+    for (size_t i = 0; i < _frames.size(); ++i) {
+      const FrameQualityReport& q = _frames[i];
+      t.mse_y += q.mse_y, t.mse_u += q.mse_u, t.mse_v += q.mse_v, t.ssim += q.ssim_y;
+      t.mse_all += mse_all(q);
+      if (q.psnr_y < t.min_psnr_y) t.min_psnr_y = q.psnr_y, t.min_frame = i;
+    }
+    t.mse_y /= n, t.mse_u /= n, t.mse_v /= n, t.mse_all /= n, t.ssim /= n;
+    return t;
+  }
+  double psnr(double mse) const { return mse == 0 ? double(INFINITY) : 10.0 * std::log10(_peak2 / mse); }
+  void print_stream() const {
+    if (_frames.empty()) return;
+    const Totals t = totals();
+    std::cout << "stream, " << _frames.size() << " frames: mse y " << num(t.mse_y) << " u " << num(t.mse_u) << " v "
+              << num(t.mse_v) << " all " << num(t.mse_all) << std::endl
+              << "stream, " << _frames.size() << " frames: psnr y " << num(psnr(t.mse_y)) << " dB u "
+              << num(psnr(t.mse_u)) << " dB v " << num(psnr(t.mse_v)) << " dB all " << num(psnr(t.mse_all))
+              << " dB ssim " << num(t.ssim) << std::endl
+              << "lowest psnr y: " << num(t.min_psnr_y) << " dB at frame " << t.min_frame << std::endl;
+  }
+  void write_json(const std::string& path) const {
+    std::ofstream out(path);
+    if (!out) throw srcnn::IOException("cannot write report '" + path + "'");
+    out << "{\n  \"width\": " << _hd.w << ", \"height\": " << _hd.h << ", \"bits\": " << _hd.bits
+        << ", \"chroma\": \"" << _hd.chroma << "\", \"shave\": " << _shave << ",\n  \"frames\": [\n";
+    for (size_t i = 0; i < _frames.size(); ++i) {
+      const FrameQualityReport& q = _frames[i];
+      out << "    {\"frame\": " << i << ", \"mse_y\": " << json_num(q.mse_y) << ", \"psnr_y\": " << json_num(q.psnr_y)
+          << ", \"ssim_y\": " << json_num(q.ssim_y) << ", \"mse_u\": " << json_num(q.mse_u)
+          << ", \"psnr_u\": " << json_num(q.psnr_u) << ", \"mse_v\": " << json_num(q.mse_v)
+          << ", \"psnr_v\": " << json_num(q.psnr_v) << ", \"psnr_all\": " << json_num(q.psnr_all) << "}"
+          << (i + 1 < _frames.size() ? "," : "") << "\n";
+    }
+    const Totals t = totals();
+    out << "  ],\n  \"stream\": {\"count\": " << _frames.size();
+    if (!_frames.empty())
+      out << ", \"mse_y\": " << json_num(t.mse_y) << ", \"mse_u\": " << json_num(t.mse_u)
+          << ", \"mse_v\": " << json_num(t.mse_v) << ", \"mse_all\": " << json_num(t.mse_all)
+          << ", \"psnr_y\": " << json_num(psnr(t.mse_y)) << ", \"psnr_u\": " << json_num(psnr(t.mse_u))
+          << ", \"psnr_v\": " << json_num(psnr(t.mse_v)) << ", \"psnr_all\": " << json_num(psnr(t.mse_all))
+          << ", \"ssim_y\": " << json_num(t.ssim) << ", \"min_psnr_y\": " << json_num(t.min_psnr_y)
+          << ", \"min_psnr_y_frame\": " << t.min_frame;
+    out << "}\n}\n";
+    out.flush();
+    if (!out) throw srcnn::IOException("cannot write report '" + path + "'");
+    std::cout << "Saving report to: '" << path << "'" << std::endl;
+  }
+
+ private:
+  double mse_all(const FrameQualityReport& q) const {
+    return ((q.mse_y * _ny + q.mse_u * _nc) + q.mse_v * _nc) / (_ny + 2 * _nc);
+  }
+  srcnn::y4m::Header _hd;
+  unsigned _shave;
+  double _ny, _nc, _peak2;
+  std::vector<FrameQualityReport> _frames;
+};
+
+/** TRUTH / REF against the stream it is measured with: size, subsampling and
+ * depth must agree (one message, before any frame is read) */
+void check_same_geometry(const std::string& name_a, const srcnn::y4m::Header& a, const std::string& name_b,
+                         const srcnn::y4m::Header& b) {
+  auto desc = [](const srcnn::y4m::Header& h) {
+    return std::to_string(h.w) + "x" + std::to_string(h.h) + " " + std::to_string(h.cx) + "x" +
+           std::to_string(h.cy) + " chroma subsampling, " + std::to_string(h.bits) + " bits";
+  };
+  if (a.w != b.w || a.h != b.h || a.cx != b.cx || a.cy != b.cy || a.bits != b.bits)
+    throw std::runtime_error("the streams differ in size, subsampling or bit depth: '" + name_a + "' is " + desc(a) +
+                             ", '" + name_b + "' is " + desc(b));
+}
 
 /** `cnn upscale` on a Y4M stream: every frame through srcnn_upscale_frame
  * (--scale) or srcnn_upscale_frame_to (--size).  Any
@@ -493,6 +657,19 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   const size_t ws_bytes = a.size_set ? p.super_resolve_frame_to_workspace_bytes(hd.w, hd.h, ohd.w, ohd.h)
                                      : p.super_resolve_yuv_workspace_bytes(hd.w, hd.h, a.scale);
   srcnn::require(ws_bytes > 0, std::string("upscale: ") + srcnn_last_error());
+  // --ref: the truth stream, measured against every output frame where it lies
+  const bool measure = !a.ref.empty();
+  std::ifstream truth;
+  size_t qws_bytes = 0;
+  if (measure) {
+    truth.open(a.ref, std::ios::binary);
+    if (!truth) throw srcnn::IOException("cannot open '" + a.ref + "'");
+    check_same_geometry("the output of " + a.in, ohd, a.ref, y4m::read_header(truth));
+    StreamQuality::check(ohd, a.shave);
+    qws_bytes = srcnn_quality_frame_workspace_bytes(ohd.w, ohd.h, ohd.cx, ohd.cy, a.shave);
+    std::cout << "Measuring against: " << a.ref << ", shave: " << a.shave << std::endl;
+  }
+  StreamQuality report(ohd, a.shave);
   std::ofstream out;
   const bool store = !a.dry && !a.out.empty();
   if (store) {
@@ -503,13 +680,21 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   // profile mode: both slots on the pipeline's stream, where the calls are timed
   const bool own_streams = !a.profile;
   FrameSlot slots[2];
-  for (unsigned i = 0; i < a.slots; ++i) slots[i].init(hd, ohd, ws_bytes, own_streams);
+  for (unsigned i = 0; i < a.slots; ++i) {
+    slots[i].init(hd, ohd, ws_bytes, own_streams);
+    if (measure) slots[i].init_ref(ohd, qws_bytes);
+  }
   auto stream_of = [&](FrameSlot& s) { return own_streams ? s.stream : p.context()->stream(); };
   size_t written = 0;
   // the slot's frame back to the host (the copy waits for the slot's work) and out
   auto drain = [&](FrameSlot& s) {
     if (!s.busy) return;
-    srcnn::check(srcnn_memcpy_d2h(s.host_out, s.dev_out, ohd.frame_bytes(), stream_of(s)), "memcpy_d2h");
+    if (store || !measure)
+      srcnn::check(srcnn_memcpy_d2h(s.host_out, s.dev_out, ohd.frame_bytes(), stream_of(s)), "memcpy_d2h");
+    if (measure) {  // the 8 doubles return with the frame
+      srcnn::check(srcnn_memcpy_d2h(s.host_res, s.dev_res, 8 * sizeof(double), stream_of(s)), "memcpy_d2h");
+      report.add(static_cast<const double*>(s.host_res));
+    }
     s.busy = false;
     if (store) y4m::write_frame(out, ohd, static_cast<const unsigned char*>(s.host_out));
     ++written;
@@ -527,12 +712,29 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
       rc = 1;
       break;
     }
+    if (measure) {
+      try {
+        if (!y4m::read_frame(truth, ohd, static_cast<unsigned char*>(s.host_ref))) {
+          std::cout << "[ERROR] '" << a.ref << "' ends after " << k << " frames, before '" << a.in << "'" << std::endl;
+          rc = 1;
+          break;
+        }
+      } catch (const srcnn::IOException& e) {
+        std::cout << "[ERROR] '" << a.ref << "' frame " << k << ": " << e.what() << std::endl;
+        rc = 1;
+        break;
+      }
+      srcnn::check(srcnn_memcpy_h2d(s.dev_ref, s.host_ref, ohd.frame_bytes(), stream_of(s)), "memcpy_h2d");
+    }
     srcnn::check(srcnn_memcpy_h2d(s.dev_in, s.host_in, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
     if (a.size_set)
       p.super_resolve_frame_to(fmt, s.src, s.dst, hd.w, hd.h, ohd.w, ohd.h, s.ws, ws_bytes,
                                own_streams ? s.stream : nullptr);
     else
       p.super_resolve_frame(fmt, s.src, s.dst, hd.w, hd.h, a.scale, s.ws, ws_bytes, own_streams ? s.stream : nullptr);
+    if (measure)
+      p.quality_frame(fmt, s.dst, fmt, s.ref, ohd.w, ohd.h, a.shave, static_cast<double*>(s.dev_res), s.qws,
+                      qws_bytes, own_streams ? s.stream : nullptr);
     s.busy = true;
   }
   for (unsigned i = 0; i < a.slots; ++i) drain(slots[(k + i) % a.slots]);  // the oldest first
@@ -543,6 +745,7 @@ int upscale_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   std::cout << "Frames: " << written << ", " << (sec > 0 ? double(written) / sec : 0.0) << " frames per second"
             << (store ? ", saved to '" + a.out + "'" : std::string()) << std::endl;
+  if (measure) report.print_stream();
   p.context()->block();
   return rc;
 }
@@ -591,19 +794,107 @@ int downscale(DataPipeline& p, const Args& a) {
   return 0;
 }
 
-/** doubles as the reports print them: 17 significant digits, so that a reader
- * gets the device's value back bit for bit; "inf" for identical images */
-std::string num(double v) {
-  if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
-  char buf[40];
-  std::snprintf(buf, sizeof(buf), "%.17g", v);
-  return buf;
-}
-/** the same for the JSON report, which has no infinity: null */
-std::string json_num(double v) { return std::isfinite(v) ? num(v) : "null"; }
+/** One pair of frames in flight of `cnn quality` on two Y4M streams: its own
+ * stream, pinned host frames, device frames, the metric's workspace and its 8
+ * doubles on the device and in pinned memory.  Released when the slot goes. */
+struct QualitySlot {
+  srcnn_stream_t stream = nullptr;
+  void *host_a = nullptr, *host_b = nullptr, *host_res = nullptr;  // pinned
+  void *dev_a = nullptr, *dev_b = nullptr, *ws = nullptr, *dev_res = nullptr;
+  srcnn_yuv_frame a{}, b{};
+  bool busy = false;  // a pair is enqueued and not yet reported
 
-/** `cnn quality`: the image against --ref through srcnn_quality */
+  QualitySlot() = default;
+  QualitySlot(const QualitySlot&) = delete;
+  QualitySlot& operator=(const QualitySlot&) = delete;
+  ~QualitySlot() {
+    if (stream) srcnn_stream_sync(stream);
+    for (void* d : {dev_a, dev_b, ws, dev_res}) srcnn_free(d);
+    for (void* h : {host_a, host_b, host_res}) srcnn_host_free(h);
+    if (stream) srcnn_stream_destroy(stream);
+  }
+  void init(const srcnn::y4m::Header& hd, size_t ws_bytes, bool own_stream) {
+    if (own_stream) srcnn::check(srcnn_stream_create(&stream), "stream_create");
+    for (void** h : {&host_a, &host_b}) srcnn::check(srcnn_host_alloc(h, hd.frame_bytes()), "host_alloc");
+    srcnn::check(srcnn_host_alloc(&host_res, 8 * sizeof(double)), "host_alloc");
+    for (void** d : {&dev_a, &dev_b}) srcnn::check(srcnn_malloc(d, hd.frame_bytes()), "malloc");
+    srcnn::check(srcnn_malloc(&ws, ws_bytes), "malloc");
+    srcnn::check(srcnn_malloc(&dev_res, 8 * sizeof(double)), "malloc");
+    a = FrameSlot::planes(dev_a, hd);
+    b = FrameSlot::planes(dev_b, hd);
+  }
+};
+
+/** `cnn quality` on two Y4M streams: every pair of frames through
+ * srcnn_quality_frame, two pairs in flight as upscale_y4m keeps two frames */
+int quality_y4m(DataPipeline& p, const Args& a, std::istream& in) {
+  namespace y4m = srcnn::y4m;
+  const y4m::Header hd = y4m::read_header(in);
+  if (!is_y4m(a.ref)) throw std::runtime_error("'" + a.ref + "' is not a Y4M video (no YUV4MPEG2 magic)");
+  std::ifstream rin(a.ref, std::ios::binary);
+  const y4m::Header rhd = y4m::read_header(rin);
+  check_same_geometry(a.in, hd, a.ref, rhd);
+  StreamQuality::check(hd, a.shave);
+  const size_t ws_bytes = srcnn_quality_frame_workspace_bytes(hd.w, hd.h, hd.cx, hd.cy, a.shave);
+  // the range is validated and enters no arithmetic: both sides take IN's
+  const srcnn_yuv_format fmt{hd.bits, 0, SRCNN_YUV_PLANAR, hd.cx, hd.cy, hd.full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED};
+  std::cout << "Y4M videos: " << hd.w << "x" << hd.h << " C" << hd.chroma << ", " << hd.bits << " bits" << std::endl;
+  const bool own_streams = !a.profile;  // profile mode: the context's stream, where the calls are timed
+  StreamQuality report(hd, a.shave);
+  QualitySlot slots[2];
+  for (auto& s : slots) s.init(hd, ws_bytes, own_streams);
+  auto stream_of = [&](QualitySlot& s) { return own_streams ? s.stream : p.context()->stream(); };
+  auto drain = [&](QualitySlot& s) {
+    if (!s.busy) return;
+    srcnn::check(srcnn_memcpy_d2h(s.host_res, s.dev_res, 8 * sizeof(double), stream_of(s)), "memcpy_d2h");
+    s.busy = false;
+    report.add(static_cast<const double*>(s.host_res));
+  };
+  int rc = 0;
+  size_t k = 0;
+  for (; !a.frames_set || k < a.frames; ++k) {
+    QualitySlot& s = slots[k % 2];
+    drain(s);  // pair k - 2: reported before its slot is reused, so the lines come in order
+    try {
+      const bool more_a = y4m::read_frame(in, hd, static_cast<unsigned char*>(s.host_a));
+      const bool more_b = y4m::read_frame(rin, rhd, static_cast<unsigned char*>(s.host_b));
+      if (!more_a && !more_b) break;
+      if (more_a != more_b) {
+        const std::string &shorter = more_a ? a.ref : a.in, &longer = more_a ? a.in : a.ref;
+        std::cout << "[ERROR] '" << shorter << "' ends after " << k << " frames, before '" << longer << "'" << std::endl;
+        rc = 1;
+        break;
+      }
+    } catch (const srcnn::IOException& e) {
+      std::cout << "[ERROR] frame " << k << ": " << e.what() << std::endl;
+      rc = 1;
+      break;
+    }
+    srcnn::check(srcnn_memcpy_h2d(s.dev_a, s.host_a, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
+    srcnn::check(srcnn_memcpy_h2d(s.dev_b, s.host_b, hd.frame_bytes(), stream_of(s)), "memcpy_h2d");
+    p.quality_frame(fmt, s.a, fmt, s.b, hd.w, hd.h, a.shave, static_cast<double*>(s.dev_res), s.ws, ws_bytes,
+                    own_streams ? s.stream : nullptr);
+    s.busy = true;
+  }
+  for (unsigned i = 0; i < 2; ++i) drain(slots[(k + i) % 2]);  // the older first
+  report.print_stream();
+  if (!a.dry && !a.out.empty()) report.write_json(a.out);
+  p.context()->block();
+  return rc;
+}
+
+/** `cnn quality`: the image against --ref through srcnn_quality, or a Y4M
+ * video against another through srcnn_quality_frame */
 int quality(DataPipeline& p, const Args& a) {
+  {
+    std::ifstream in(a.in, std::ios::binary);
+    char magic[9] = {};
+    if (in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0) {
+      in.seekg(0);
+      return quality_y4m(p, a, in);
+    }
+  }
+  if (a.frames_set) throw std::runtime_error("--frames needs a Y4M input");
   ImageData img, ref;
   srcnn::image::load(a.in, img, 4);
   srcnn::image::load(a.ref, ref, 4);
@@ -1055,7 +1346,8 @@ int main(int argc, char** argv) {
     usage();
     return 1;
   }
-  if (!a.dry && a.out.empty() && !a.quality && !a.evaluate) {  // (those two print their result)
+  if (!a.dry && a.out.empty() && !a.quality && !a.evaluate &&
+      !(a.upscale && !a.ref.empty())) {  // (those print their result)
     std::cout << "Either provide out path or do the dry run" << std::endl;
     return 1;
   }

@@ -127,6 +127,8 @@ SIGNATURES = {
     "srcnn_make_pairs": (_I, [_P, _U, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_quality_workspace_bytes": (_S, [_U, _U, _U]),
     "srcnn_quality": (_I, [_P, _I, _U, _P, _I, _U, _U, _U, _U, _P, _P, _S, _P]),
+    "srcnn_quality_frame_workspace_bytes": (_S, [_U, _U, _U, _U, _U]),
+    "srcnn_quality_frame": (_I, [_MP, _FP, _MP, _FP, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_upscale_yuv_workspace_bytes": (_S, [_NP, _U, _U, _U]),
@@ -677,6 +679,21 @@ def upscale_frame(net, fmt, src, dst, w, h, scale, params, ws, ws_bytes, s=None)
     the workspace is upscale_yuv_workspace_bytes (srcnn_upscale_frame)."""
     _call("srcnn_upscale_frame", ctypes.byref(net), ctypes.byref(fmt) if fmt is not None else None,
           ctypes.byref(src), ctypes.byref(dst), w, h, scale, ptr(params), ptr(ws), ws_bytes, s)
+
+
+def quality_frame_workspace_bytes(w, h, cx=2, cy=2, shave=0):
+    return _lib.srcnn_quality_frame_workspace_bytes(w, h, cx, cy, shave)
+
+
+def quality_frame(fmt_a, a, fmt_b, b, w, h, shave, result, ws, ws_bytes, s=None):
+    """{mse_y, psnr_y, ssim_y, mse_u, psnr_u, mse_v, psnr_v, psnr_all} (8
+    doubles, device) of two Y'CbCr frames of w x h luma samples, each a
+    YuvFrame with its own YuvFormat (equal bits, cx, cy and range; msb, layout
+    and pitches may differ), `shave` luma pixels dropped per side: PSNR of the
+    integer code values per plane, SSIM on luma (srcnn_quality_frame)."""
+    ref = lambda x: ctypes.byref(x) if x is not None else None
+    _call("srcnn_quality_frame", ref(fmt_a), ref(a), ref(fmt_b), ref(b), w, h, shave, ptr(result), ptr(ws),
+          ws_bytes, s)
 
 
 def upscale_to_workspace_bytes(net, w, h, W, H):

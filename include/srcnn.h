@@ -503,7 +503,8 @@ typedef struct srcnn_net {
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
  * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale,
  * srcnn_upscale_yuv, srcnn_upscale_to, srcnn_upscale_frame_to) launch for this
- * net, and the kernels of srcnn_make_pairs and srcnn_quality.
+ * net, and the kernels of srcnn_make_pairs, srcnn_quality and
+ * srcnn_quality_frame.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -534,8 +535,8 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     rgb: 3*W*H bytes; srcnn_upscale_yuv: the row bytes of dst's three
  *     planes, not the pitch gaps between them; srcnn_make_pairs: count*tile*tile floats of X and of
  *     T each; srcnn_gather_batch, which takes no workspace: n*tw*th floats of
- *     X and of T each and the n of means; srcnn_quality / srcnn_evaluate: the
- *     3 / 6 doubles of result);
+ *     X and of T each and the n of means; srcnn_quality / srcnn_evaluate /
+ *     srcnn_quality_frame: the 3 / 6 / 8 doubles of result);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
@@ -681,6 +682,56 @@ SRCNN_API int srcnn_upscale_frame_to(const srcnn_net* net, const srcnn_yuv_forma
                                      uint32_t w, uint32_t h, uint32_t W, uint32_t H,
                                      const float* params, void* ws, size_t ws_bytes,
                                      srcnn_stream_t stream);
+
+/* PSNR per plane and SSIM on luma of two Y'CbCr frames, on the device (an
+ * MI355X extension; DESIGN.md 17.1 is the spec).  a and b are frames of w x h
+ * luma samples with chroma [ceil(h/cy)][ceil(w/cx)], each a srcnn_yuv_frame
+ * with its own srcnn_yuv_format: byte addresses and pitches in bytes as in
+ * srcnn_upscale_frame.  bits, cx, cy and range must be equal in the two
+ * formats; msb, layout and every pitch may differ (a P010 frame against a
+ * planar 10-bit one).  A sample's value is its integer code x (DESIGN.md 15:
+ * the byte, the 16-bit word, or the word >> (16 - bits) for msb = 1); the
+ * range is validated and enters no arithmetic.  `shave` luma pixels are
+ * dropped on all four sides, Ws = w - 2*shave and Hs = h - 2*shave at least
+ * 11, and ceil(shave/cx) columns and ceil(shave/cy) rows per side of the
+ * chroma planes.
+ *
+ * result (device, 8 doubles) = {mse_y, psnr_y, ssim_y, mse_u, psnr_u, mse_v,
+ * psnr_v, psnr_all}: mse_p = (double)S_p / (double)N_p with S_p the sum over
+ * the plane's N_p samples of the integer (xa - xb)^2, summed as an unsigned
+ * 64-bit integer and so exact; psnr_p = 10 log10((2^bits - 1)^2 / mse_p), +inf
+ * for S_p == 0; psnr_all likewise from (((double)S_y + (double)S_u) +
+ * (double)S_v) / (double)(N_y + N_u + N_v); ssim_y = srcnn_quality's SSIM of
+ * the lumas x * 2^-(bits - 8), exact in fp32 and in [0, 256): SSIM at the
+ * dynamic range 255 * 2^(bits - 8), on purpose not 2^bits - 1.  Identical
+ * frames give exactly {0, +inf, 1, 0, +inf, 0, +inf, +inf}.  No atomics: the
+ * order of the SSIM sum depends on (Ws, Hs) alone, so that the luma results
+ * with shave = k are bit-identical to the call on the pointer-offset interior
+ * with shave = 0, whatever the layouts and pitches, and two calls on the same
+ * inputs are bit-identical.
+ *
+ * `ws` (srcnn_quality_frame_workspace_bytes: two 8-byte words per luma
+ * workgroup, one per chroma workgroup and plane) falls under the memory
+ * contract at srcnn_train_workspace_bytes; the call writes the eight doubles
+ * of result and reads a and b inside the shaved windows only, never between
+ * the rows.  Stream-ordered, three launches, no host synchronisation, no
+ * allocation.
+ *
+ * SRCNN_ERR_INVALID, before any launch: a null format, frame, result or
+ * workspace; in a format or frame whatever srcnn_upscale_frame rejects (bits
+ * outside 8..16, msb, layout, subsampling, range, a null plane or a v plane
+ * of a semi-planar frame, an odd address or pitch of two-byte samples, a pitch
+ * below the row's bytes); formats that differ in bits, cx, cy or range; Ws <
+ * 11 or Hs < 11 (2*shave wrapping around included); an empty chroma window;
+ * result or ws not 8-byte aligned; more than 2^31-1 samples in a plane.
+ * SRCNN_ERR_WORKSPACE for a workspace that is too small;
+ * srcnn_quality_frame_workspace_bytes returns 0 for invalid sizes. */
+SRCNN_API size_t srcnn_quality_frame_workspace_bytes(uint32_t w, uint32_t h, uint32_t cx,
+                                                     uint32_t cy, uint32_t shave);
+SRCNN_API int srcnn_quality_frame(const srcnn_yuv_format* fmt_a, const srcnn_yuv_frame* a,
+                                  const srcnn_yuv_format* fmt_b, const srcnn_yuv_frame* b,
+                                  uint32_t w, uint32_t h, uint32_t shave, double* result,
+                                  void* ws, size_t ws_bytes, srcnn_stream_t stream);
 
 /* "How many dB over bicubic?" in one call: the full-size ground truth rgba
  * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at
