@@ -270,7 +270,8 @@ int srcnn_preload(const srcnn_net* net) {
   if ((rc = srcnn::fused::preload(net)) < 0 || (rc = srcnn::fused::preload_forward(net)) < 0 ||
       (rc = srcnn::wide::preload(net)) < 0 || (rc = srcnn::preload_upscale()) < 0 ||
       (rc = srcnn::preload_pairs()) < 0 || (rc = srcnn::preload_quality()) < 0 ||
-      (rc = srcnn::preload_yuv()) < 0 || (rc = srcnn::preload_resize()) < 0)
+      (rc = srcnn::preload_yuv()) < 0 || (rc = srcnn::preload_yuv_down()) < 0 ||
+      (rc = srcnn::preload_resize()) < 0)
     return rc;
   return srcnn::preload_update();
 }

@@ -584,6 +584,170 @@ int eval_ws(const srcnn_net* net, uint32_t W, uint32_t H, uint32_t scale, int64_
   return SRCNN_OK;
 }
 
+// ---- the down direction of the video family ----
+// srcnn_downscale_planes behind its entry point and the frame-level calls
+int down_planes(const char* who, const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
+                uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
+                uint32_t scale, uint32_t bits, uint32_t msb, uint32_t layout, srcnn_stream_t stream) {
+  uint32_t B;
+  if (int rc = yuv_samples(who, bits, msb, &B)) return rc;
+  if (int rc = yuv_layout(who, layout)) return rc;
+  const bool semi = layout == SRCNN_YUV_SEMIPLANAR;
+  if (int rc = check_scale(who, scale)) return rc;
+  if (int rc = plane_dims(who, pw, ph, src_pitch, B, semi ? 2 : 1)) return rc;
+  if (int rc = plane_dims(who, ow, oh, dst_pitch, B, semi ? 2 : 1)) return rc;
+  SRCNN_REQUIRE(ow <= (pw - 1) / scale + 1 && oh <= (ph - 1) / scale + 1,
+                "%s: output %ux%u exceeds ceil(%u / %u) x ceil(%u / %u)", who, ow, oh, pw, scale, ph, scale);
+  SRCNN_REQUIRE(src0 && dst0, "%s: null buffer", who);
+  if (semi) {
+    SRCNN_REQUIRE(!src1 && !dst1, "%s: a semi-planar frame has no second chroma plane", who);
+  } else {
+    SRCNN_REQUIRE(!src1 == !dst1, "%s: exactly one of src1 and dst1 is null", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, src0) && !odd_address(B, src1) && !odd_address(B, dst0) &&
+                    !odd_address(B, dst1),
+                "%s: odd address of two-byte samples", who);
+  return srcnn::downscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale, bits,
+                                 msb != 0, semi, as_stream(stream));
+}
+
+// a frame format as srcnn_upscale_frame checks one; *B: bytes per sample,
+// *nch: samples per chroma pixel of a chroma plane
+int frame_format(const char* who, const srcnn_yuv_format* fmt, uint32_t* B, uint32_t* nch) {
+  SRCNN_REQUIRE(fmt, "%s: null srcnn_yuv_format", who);
+  SRCNN_REQUIRE(known_subsampling(fmt->cx, fmt->cy),
+                "%s: chroma subsampling %ux%u is not 2x2 (4:2:0), 2x1 (4:2:2) or 1x1 (4:4:4)", who, fmt->cx,
+                fmt->cy);
+  if (int rc = yuv_range(who, fmt->range)) return rc;
+  if (int rc = yuv_samples(who, fmt->bits, fmt->msb, B)) return rc;
+  if (int rc = yuv_layout(who, fmt->layout)) return rc;
+  *nch = fmt->layout == SRCNN_YUV_SEMIPLANAR ? 2 : 1;
+  return SRCNN_OK;
+}
+// the planes of a frame of w x h luma samples: present, aligned, pitched
+int frame_planes(const char* who, const srcnn_yuv_format& fmt, const srcnn_yuv_frame* f, uint32_t w,
+                 uint32_t h, uint32_t B, uint32_t nch) {
+  SRCNN_REQUIRE(f, "%s: null buffer", who);
+  SRCNN_REQUIRE(f->y && f->u, "%s: null plane", who);
+  if (nch == 2) {
+    SRCNN_REQUIRE(!f->v, "%s: a semi-planar frame has no v plane", who);
+  } else {
+    SRCNN_REQUIRE(f->v, "%s: null plane", who);
+  }
+  SRCNN_REQUIRE(!odd_address(B, f->y) && !odd_address(B, f->u) && !odd_address(B, f->v),
+                "%s: odd address of two-byte samples", who);
+  if (int rc = plane_dims(who, w, h, f->pitch_y, B)) return rc;
+  return plane_dims(who, (w - 1) / fmt.cx + 1, (h - 1) / fmt.cy + 1, f->pitch_c, B, nch);
+}
+// the source W x H of a frame-level downscale against the scale (the planes'
+// own limits come with their pitches); *w, *h: the small frame
+int down_frame_dims(const char* who, uint32_t W, uint32_t H, uint32_t scale, uint32_t* w, uint32_t* h) {
+  if (int rc = check_scale(who, scale)) return rc;
+  SRCNN_REQUIRE(W >= scale && H >= scale, "%s: frame %ux%u is smaller than the scale %u", who, W, H, scale);
+  *w = W / scale;
+  *h = H / scale;
+  return SRCNN_OK;
+}
+int downscale_frame(const char* who, const srcnn_yuv_format* fmt, const srcnn_yuv_frame* src,
+                    const srcnn_yuv_frame* dst, uint32_t W, uint32_t H, uint32_t scale,
+                    srcnn_stream_t stream) {
+  uint32_t B, nch, w, h;
+  if (int rc = frame_format(who, fmt, &B, &nch)) return rc;
+  if (int rc = down_frame_dims(who, W, H, scale, &w, &h)) return rc;
+  if (int rc = frame_planes(who, *fmt, src, W, H, B, nch)) return rc;
+  if (int rc = frame_planes(who, *fmt, dst, w, h, B, nch)) return rc;
+  // (every check of the two calls has been made: the crop rule holds by
+  // ceil(floor(W/s)/cx) <= ceil(ceil(W/cx)/s))
+  if (int rc = down_planes(who, src->y, nullptr, src->pitch_y, W, H, dst->y, nullptr, dst->pitch_y, w, h, scale,
+                           fmt->bits, fmt->msb, SRCNN_YUV_PLANAR, stream))
+    return rc;
+  return down_planes(who, src->u, src->v, src->pitch_c, (W - 1) / fmt->cx + 1, (H - 1) / fmt->cy + 1, dst->u,
+                     dst->v, dst->pitch_c, (w - 1) / fmt->cx + 1, (h - 1) / fmt->cy + 1, scale, fmt->bits,
+                     fmt->msb, fmt->layout, stream);
+}
+
+// regions of the make_pairs_frame workspace: small Y plane [h][w] at the pitch
+// of its row bytes | X plane [Hc][Wc] | T plane [H][W], each 256-byte aligned
+struct PairFrameWs {
+  uint32_t B, w, h, Wc, Hc;
+  size_t small, xplane, tplane, total;
+};
+int pair_frame_ws(const char* who, const srcnn_yuv_format* fmt, uint32_t W, uint32_t H, uint32_t scale,
+                  PairFrameWs* L) {
+  uint32_t nch;
+  if (int rc = frame_format(who, fmt, &L->B, &nch)) return rc;
+  if (int rc = down_frame_dims(who, W, H, scale, &L->w, &L->h)) return rc;
+  if (int rc = plane_dims(who, W, H, W * L->B, L->B)) return rc;  // (the frame's pitch comes later)
+  UpDims u;
+  if (int rc = up_dims(by_scale(who, L->w, L->h, scale), 0, false, &u)) return rc;
+  L->Wc = u.W;
+  L->Hc = u.H;
+  L->small = 0;
+  L->xplane = L->small + align_up((size_t)L->w * L->h * L->B);
+  L->tplane = L->xplane + align_up((size_t)L->Wc * L->Hc * sizeof(float));
+  L->total = L->tplane + align_up((size_t)W * H * sizeof(float));
+  return SRCNN_OK;
+}
+
+// a frame of w x h luma samples inside a workspace, rows at the pitch of their
+// bytes: y | u | v (no v: semi-planar), each 256-byte aligned, from byte `at`
+struct WsFrame {
+  size_t y, u, v, end;
+  uint32_t pitch_y, pitch_c;
+};
+WsFrame ws_frame(size_t at, const srcnn_yuv_format& fmt, uint32_t w, uint32_t h, uint32_t B, uint32_t nch) {
+  const uint32_t cw = (w - 1) / fmt.cx + 1, ch = (h - 1) / fmt.cy + 1;
+  WsFrame f;
+  f.pitch_y = w * B;
+  f.pitch_c = cw * nch * B;
+  f.y = at;
+  f.u = f.y + align_up((size_t)f.pitch_y * h);
+  f.v = f.u + align_up((size_t)f.pitch_c * ch);
+  f.end = nch == 2 ? f.v : f.v + align_up((size_t)f.pitch_c * ch);
+  return f;
+}
+srcnn_yuv_frame frame_at(char* p, const WsFrame& f, uint32_t nch) {
+  return srcnn_yuv_frame{reinterpret_cast<uint8_t*>(p + f.y), reinterpret_cast<uint8_t*>(p + f.u),
+                         nch == 2 ? nullptr : reinterpret_cast<uint8_t*>(p + f.v), f.pitch_y, f.pitch_c};
+}
+// regions of the evaluate_frame workspace: small frame | output frame | luma
+// plane [Hc][Wc] | srcnn_upscale_frame's workspace | srcnn_quality_frame's
+struct EvalFrameWs {
+  uint32_t B, nch, w, h, Wc, Hc;
+  WsFrame small, out;
+  size_t plane, up, q, total, up_bytes, q_bytes;
+};
+// every check of the calls that does not need the buffers; shave < 0: the
+// sizes alone (the workspace query: the metric's workspace is sized for shave 0)
+int eval_frame_ws(const char* who, const srcnn_net* net, const srcnn_yuv_format* fmt, uint32_t W, uint32_t H,
+                  uint32_t scale, int64_t shave, EvalFrameWs* L) {
+  SRCNN_REQUIRE(net, "%s: null srcnn_net", who);
+  if (int rc = frame_format(who, fmt, &L->B, &L->nch)) return rc;
+  if (int rc = down_frame_dims(who, W, H, scale, &L->w, &L->h)) return rc;
+  // the truth's planes at the pitch of their bytes (its own pitches come later)
+  if (int rc = plane_dims(who, W, H, W * L->B, L->B)) return rc;
+  const uint32_t CW = (W - 1) / fmt->cx + 1, CH = (H - 1) / fmt->cy + 1;
+  if (int rc = plane_dims(who, CW, CH, CW * L->nch * L->B, L->B, L->nch)) return rc;
+  FrameDims f;
+  UpWs U;
+  if (int rc = frame_dims(by_scale(who, L->w, L->h, scale), net, fmt->cx, fmt->cy, &f)) return rc;
+  if (!up_ws(net, f.d, &U)) return SRCNN_ERR_INVALID;  // (message from net_dims)
+  L->up_bytes = U.total;
+  L->Wc = f.d.W;
+  L->Hc = f.d.H;
+  FrameQualityDims q;
+  if (int rc = quality_frame_dims(who, L->Wc, L->Hc, fmt->cx, fmt->cy, shave < 0 ? 0 : (uint32_t)shave, &q))
+    return rc;
+  L->q_bytes = srcnn_quality_frame_workspace_bytes(L->Wc, L->Hc, fmt->cx, fmt->cy, 0);
+  L->small = ws_frame(0, *fmt, L->w, L->h, L->B, L->nch);
+  L->out = ws_frame(L->small.end, *fmt, L->Wc, L->Hc, L->B, L->nch);
+  L->plane = L->out.end;
+  L->up = L->plane + align_up((size_t)L->Wc * L->Hc * sizeof(float));
+  L->q = L->up + align_up(L->up_bytes);
+  L->total = L->q + align_up(L->q_bytes);
+  return SRCNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -667,6 +831,20 @@ int srcnn_resize_planes(const void* src0, const void* src1, uint32_t src_pitch, 
                        PlaneMap{false, 0, rx_num, rx_den, ry_num, ry_den}, bits, msb, layout, stream);
 }
 
+int srcnn_downscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw,
+                           uint32_t ph, void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow,
+                           uint32_t oh, uint32_t scale, uint32_t bits, uint32_t msb, uint32_t layout,
+                           srcnn_stream_t stream) {
+  return down_planes("downscale_planes", src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale,
+                     bits, msb, layout, stream);
+}
+
+int srcnn_downscale_frame(const srcnn_yuv_format* fmt, const srcnn_yuv_frame* src,
+                          const srcnn_yuv_frame* dst, uint32_t W, uint32_t H, uint32_t scale,
+                          srcnn_stream_t stream) {
+  return downscale_frame("downscale_frame", fmt, src, dst, W, H, scale, stream);
+}
+
 int srcnn_downscale_rgba(const uint8_t* rgba, uint8_t* small, uint32_t W, uint32_t H,
                          uint32_t scale, srcnn_stream_t stream) {
   if (int rc = down_dims("downscale_rgba", W, H, scale)) return rc;
@@ -743,6 +921,50 @@ int srcnn_make_pairs(const uint8_t* rgba, uint32_t W, uint32_t H, uint32_t scale
   if ((rc = srcnn_extract_luma(rgba, tplane, W, H, 1, stream))) return rc;
   if ((rc = srcnn_gather_tiles(xplane, L.Wc, L.Hc, 0, 0, stride, nx, ny, tile, tile, 1, X, nullptr,
                                stream)))
+    return rc;
+  return srcnn_gather_tiles(tplane, W, H, 0, 0, stride, nx, ny, tile, tile, 0, T, nullptr, stream);
+}
+
+size_t srcnn_make_pairs_frame_workspace_bytes(const srcnn_yuv_format* fmt, uint32_t W, uint32_t H,
+                                              uint32_t scale) {
+  PairFrameWs L;
+  return pair_frame_ws("make_pairs_frame", fmt, W, H, scale, &L) ? 0 : L.total;
+}
+
+int srcnn_make_pairs_frame(const srcnn_yuv_format* fmt, const srcnn_yuv_frame* frame, uint32_t W,
+                           uint32_t H, uint32_t scale, uint32_t tile, uint32_t stride, float* X,
+                           float* T, void* ws, size_t ws_bytes, srcnn_stream_t stream) {
+  const char* who = "make_pairs_frame";
+  PairFrameWs L;
+  if (int rc = pair_frame_ws(who, fmt, W, H, scale, &L)) return rc;
+  SRCNN_REQUIRE(tile > 0 && stride > 0, "%s: tile(%u) and stride(%u) must be > 0", who, tile, stride);
+  uint32_t nx, ny;
+  SRCNN_REQUIRE(srcnn_make_pairs_count(W, H, scale, tile, stride, &nx, &ny) > 0,
+                "%s: frame %ux%u at scale %u holds no %ux%u tile (or more than 2^31-1)", who, W, H, scale,
+                tile, tile);
+  if (int rc = gather_dims(who, L.Wc, L.Hc, 0, 0, stride, nx, ny, tile, tile)) return rc;
+  if (int rc = gather_dims(who, W, H, 0, 0, stride, nx, ny, tile, tile)) return rc;
+  SRCNN_REQUIRE(frame && X && T && ws, "%s: null buffer", who);
+  SRCNN_REQUIRE(frame->y, "%s: null plane", who);
+  SRCNN_REQUIRE(!odd_address(L.B, frame->y) && !odd_address(L.B, ws), "%s: odd address of two-byte samples",
+                who);
+  if (int rc = plane_dims(who, W, H, frame->pitch_y, L.B)) return rc;
+  if (ws_bytes < L.total) return fail(SRCNN_ERR_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  uint8_t* small = reinterpret_cast<uint8_t*>(p + L.small);
+  float* xplane = reinterpret_cast<float*>(p + L.xplane);
+  float* tplane = reinterpret_cast<float*>(p + L.tplane);
+  int rc;
+  if ((rc = srcnn_downscale_planes(frame->y, nullptr, frame->pitch_y, W, H, small, nullptr, L.w * L.B, L.w, L.h,
+                                   scale, fmt->bits, fmt->msb, SRCNN_YUV_PLANAR, stream)))
+    return rc;
+  if ((rc = srcnn_yuv_upscale_luma16(small, L.w * L.B, xplane, L.w, L.h, scale, 0, fmt->bits, fmt->msb,
+                                     fmt->range, stream)))
+    return rc;
+  if ((rc = srcnn_yuv_upscale_luma16(frame->y, frame->pitch_y, tplane, W, H, 1, 0, fmt->bits, fmt->msb,
+                                     fmt->range, stream)))
+    return rc;
+  if ((rc = srcnn_gather_tiles(xplane, L.Wc, L.Hc, 0, 0, stride, nx, ny, tile, tile, 1, X, nullptr, stream)))
     return rc;
   return srcnn_gather_tiles(tplane, W, H, 0, 0, stride, nx, ny, tile, tile, 0, T, nullptr, stream);
 }
@@ -901,6 +1123,44 @@ int srcnn_evaluate(const srcnn_net* net, const uint8_t* rgba, uint32_t W, uint32
   if ((rc = srcnn_upscale_compose(small, plane, rgb, L.w, L.h, scale, stream))) return rc;
   return srcnn_quality(rgb, SRCNN_PIX_RGB8, L.Wc, rgba, SRCNN_PIX_RGBA8, W, L.Wc, L.Hc, shave,
                        result + 3, p + L.q, L.q_bytes, stream);
+}
+
+size_t srcnn_evaluate_frame_workspace_bytes(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                                            uint32_t W, uint32_t H, uint32_t scale) {
+  EvalFrameWs L;
+  return eval_frame_ws("evaluate_frame", net, fmt, W, H, scale, -1, &L) ? 0 : L.total;
+}
+
+int srcnn_evaluate_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                         const srcnn_yuv_frame* truth, uint32_t W, uint32_t H, uint32_t scale,
+                         uint32_t shave, const float* params, double* result, void* ws,
+                         size_t ws_bytes, srcnn_stream_t stream) {
+  const char* who = "evaluate_frame";
+  EvalFrameWs L;
+  if (int rc = eval_frame_ws(who, net, fmt, W, H, scale, shave, &L)) return rc;
+  SRCNN_REQUIRE(truth && params && result && ws, "%s: null buffer", who);
+  if (int rc = frame_planes(who, *fmt, truth, W, H, L.B, L.nch)) return rc;
+  SRCNN_REQUIRE((((uintptr_t)result | (uintptr_t)ws) & 7) == 0,
+                "%s: result and workspace must be 8-byte aligned", who);
+  if (ws_bytes < L.total) return fail(SRCNN_ERR_WORKSPACE, "%s: workspace %zu B < %zu B", who, ws_bytes, L.total);
+  char* p = static_cast<char*>(ws);
+  const srcnn_yuv_frame small = frame_at(p, L.small, L.nch), out = frame_at(p, L.out, L.nch);
+  float* plane = reinterpret_cast<float*>(p + L.plane);
+  int rc;
+  if ((rc = srcnn_downscale_frame(fmt, truth, &small, W, H, scale, stream))) return rc;
+  if ((rc = srcnn_upscale_frame(net, fmt, &small, &out, L.w, L.h, scale, params, p + L.up, L.up_bytes, stream)))
+    return rc;
+  // the net's result against the truth's top-left Wc x Hc samples (its own pitches)
+  if ((rc = srcnn_quality_frame(fmt, &out, fmt, truth, L.Wc, L.Hc, shave, result, p + L.q, L.q_bytes, stream)))
+    return rc;
+  // plain bicubic: the same resampling without the net; the chroma planes stay
+  if ((rc = srcnn_yuv_upscale_luma16(small.y, small.pitch_y, plane, L.w, L.h, scale, 0, fmt->bits, fmt->msb,
+                                     fmt->range, stream)))
+    return rc;
+  if ((rc = srcnn_yuv_compose_luma16(plane, out.y, out.pitch_y, L.Wc, L.Hc, fmt->bits, fmt->msb, fmt->range,
+                                     stream)))
+    return rc;
+  return srcnn_quality_frame(fmt, &out, fmt, truth, L.Wc, L.Hc, shave, result + 8, p + L.q, L.q_bytes, stream);
 }
 
 }  // extern "C"

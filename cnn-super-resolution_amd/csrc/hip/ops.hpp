@@ -271,6 +271,15 @@ int upscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint3
 int yuv_compose_luma(const float* luma, void* y, uint32_t pitch_y, uint32_t W, uint32_t H,
                      uint32_t bits, bool msb, bool full_range, hipStream_t s);
 int preload_yuv();
+// yuv_down.hip: the antialiased bicubic / scale (1..4) of a frame's planes of
+// code values: [ph][pw] -> [oh][ow], ow <= ceil(pw / scale), oh
+// likewise, rounded to nearest even and clamped; samples, pitches and
+// semiplanar as in upscale_planes; planar with src1 == dst1 == nullptr: one
+// plane
+int downscale_planes(const void* src0, const void* src1, uint32_t src_pitch, uint32_t pw, uint32_t ph,
+                     void* dst0, void* dst1, uint32_t dst_pitch, uint32_t ow, uint32_t oh,
+                     uint32_t scale, uint32_t bits, bool msb, bool semiplanar, hipStream_t s);
+int preload_yuv_down();
 // resize.hip: the same front and back end for any output size W x H with
 // w <= W <= 4w, h <= H <= 4h: the ratio of an axis is the
 // fraction w / W; resize_planes takes it explicitly (source step per output

@@ -20,7 +20,7 @@
 // The phase is the same for every output, so every weight index is a
 // compile-time value (uniform scalar loads from __constant__).
 #include "common.hpp"
-#include "keys.hpp"
+#include "keys_down.hpp"
 #include "ops.hpp"
 
 namespace srcnn {
@@ -28,28 +28,8 @@ namespace {
 
 constexpr int kThreads = 256;
 
-// taps of scale s: source offsets o_min(s) .. s-1-o_min(s) from s*j, every
-// integer o with |o - (s-1)/2| / s < 2: 3 / 8 / 11 / 16 taps at s = 1 .. 4
-constexpr int o_min(int s) { return s % 2 ? -(3 * s + 1) / 2 + 1 : -3 * s / 2; }
-constexpr int n_taps(int s) { return s - 2 * o_min(s); }
-constexpr int kMaxTaps = n_taps(4);
-
-struct DownWeights {
-  float w[5][kMaxTaps];  // [scale][tap], computed in double, rounded once
-};
-constexpr DownWeights make_down_weights() {
-  DownWeights t{};
-  for (int s = 1; s <= 4; s++) {
-    double k[kMaxTaps] = {}, sum = 0;
-    for (int i = 0; i < n_taps(s); i++) {
-      k[i] = keys((o_min(s) + i - (s - 1) / 2.0) / s);
-      sum += k[i];
-    }
-    for (int i = 0; i < n_taps(s); i++) t.w[s][i] = (float)(k[i] / sum);
-  }
-  return t;
-}
-__constant__ DownWeights c_down = make_down_weights();
+// (o_min, n_taps and the weight table c_down: keys_down.hpp, shared with
+// yuv_down.hip)
 
 // Tile geometry by LDS budget: 32 output pixels wide, so
 // that a tile's output rows are whole 128-byte lines and its patch rows 264 -

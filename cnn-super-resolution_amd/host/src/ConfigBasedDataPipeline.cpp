@@ -420,6 +420,101 @@ size_t ConfigBasedDataPipeline::make_training_pairs(ImageData& full, unsigned sc
   return count;
 }
 
+size_t ConfigBasedDataPipeline::make_training_pairs(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& frame,
+                                                    unsigned W, unsigned H, unsigned scale, size_t tile,
+                                                    size_t stride, std::vector<SampleAllocationPool>& out) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(tile > 0 && tile <= 0xffffffffu && stride > 0 && stride <= 0xffffffffu,
+          "make_training_pairs: tile and stride must be > 0");
+  const size_t count = srcnn_make_pairs_count(W, H, scale, uint32_t(tile), uint32_t(stride), nullptr, nullptr);
+  if (count == 0) return 0;
+  const size_t ws = srcnn_make_pairs_frame_workspace_bytes(&fmt, W, H, scale);
+  require(ws > 0, std::string("make_training_pairs: ") + srcnn_last_error());
+  const size_t tile_bytes = tile * tile * sizeof(float);
+  MemoryHandle X = _context->allocate(srcnn::MEM_READ_WRITE, count * tile_bytes);
+  MemoryHandle T = _context->allocate(srcnn::MEM_READ_WRITE, count * tile_bytes);
+  void* wsp = scratch(ws);
+  if (!_make_pairs_frame_kernel)
+    _make_pairs_frame_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_make_pairs_frame");
+  {
+    srcnn::Context::Launch l(*_context, *_make_pairs_frame_kernel);
+    check(srcnn_make_pairs_frame(&fmt, &frame, W, H, scale, uint32_t(tile), uint32_t(stride), _context->fptr(X),
+                                 _context->fptr(T), wsp, ws, _context->stream()),
+          "make_pairs_frame");
+  }
+  _context->block();  // (the caller may reuse the frame)
+  out.reserve(out.size() + count);
+  for (size_t i = 0; i < count; ++i) {
+    SampleAllocationPool s;
+    s.input_luma = _context->view(X, i * tile_bytes, tile_bytes);
+    s.expected_luma = _context->view(T, i * tile_bytes, tile_bytes);
+    s.input_w = s.input_h = tile;
+    out.push_back(s);
+  }
+  return count;
+}
+
+ConfigBasedDataPipeline::TrainingGrid ConfigBasedDataPipeline::make_training_planes(
+    const srcnn_yuv_format& fmt, const srcnn_yuv_frame& frame, unsigned W, unsigned H, unsigned scale, size_t tile,
+    size_t stride) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  require(tile > 0 && tile <= 0xffffffffu && stride > 0 && stride <= 0xffffffffu,
+          "make_training_planes: tile and stride must be > 0");
+  require(_plane_tile == 0 || _plane_tile == tile, "make_training_planes: one tile size per run");
+  TrainingGrid g;
+  uint32_t nx = 0, ny = 0;
+  g.count = srcnn_make_pairs_count(W, H, scale, uint32_t(tile), uint32_t(stride), &nx, &ny);
+  if (g.count == 0) return g;
+  const size_t ws = srcnn_make_pairs_frame_workspace_bytes(&fmt, W, H, scale);
+  require(ws > 0, std::string("make_training_planes: ") + srcnn_last_error());
+  // the workspace stays: small plane | X plane [Hc][Wc] | T plane [H][W], each 256-byte aligned (srcnn.h)
+  const uint32_t w = W / scale, h = H / scale, Wc = w * scale, Hc = h * scale;
+  auto align = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t x_at = align(size_t(w) * h * (fmt.bits > 8 ? 2 : 1)), t_at = x_at + align(size_t(Wc) * Hc * sizeof(float));
+  const size_t tile_bytes = tile * tile * sizeof(float);
+  MemoryHandle planes = _context->allocate(srcnn::MEM_READ_WRITE, ws);
+  MemoryHandle X = _context->allocate(srcnn::MEM_READ_WRITE, g.count * tile_bytes);
+  MemoryHandle T = _context->allocate(srcnn::MEM_READ_WRITE, g.count * tile_bytes);
+  if (!_make_pairs_frame_kernel)
+    _make_pairs_frame_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_make_pairs_frame");
+  {
+    srcnn::Context::Launch l(*_context, *_make_pairs_frame_kernel);
+    check(srcnn_make_pairs_frame(&fmt, &frame, W, H, scale, uint32_t(tile), uint32_t(stride), _context->fptr(X),
+                                 _context->fptr(T), _context->ptr(planes), ws, _context->stream()),
+          "make_pairs_frame");
+  }
+  _context->block();  // (the tiles are released below)
+  _context->raw_memory(T)->release();
+  _context->raw_memory(X)->release();
+  char* base = static_cast<char*>(_context->ptr(planes));
+  srcnn_plane_pair p;
+  p.x = reinterpret_cast<const float*>(base + x_at);
+  p.t = reinterpret_cast<const float*>(base + t_at);
+  p.x_pitch = Wc;
+  p.t_pitch = W;
+  p.w = Wc;
+  p.h = Hc;
+  g.nx = nx, g.ny = ny, g.plane = _plane_table.size(), g.w = Wc, g.h = Hc;
+  _plane_table.push_back(p);
+  _plane_tile = tile;
+  return g;
+}
+
+size_t ConfigBasedDataPipeline::evaluate_frame_workspace_bytes(const srcnn_yuv_format& fmt, unsigned W, unsigned H,
+                                                               unsigned scale) {
+  srcnn_net nt = net();
+  return srcnn_evaluate_frame_workspace_bytes(&nt, &fmt, W, H, scale);
+}
+
+void ConfigBasedDataPipeline::evaluate_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& truth, unsigned W,
+                                             unsigned H, unsigned scale, unsigned shave, double* result, void* ws,
+                                             size_t ws_bytes, srcnn_stream_t stream) {
+  upscale_frame("evaluate_frame", "evaluate_frame", _evaluate_frame_kernel, stream,
+                [&](const srcnn_net* nt, const float* params, srcnn_stream_t s) {
+                  return srcnn_evaluate_frame(nt, &fmt, &truth, W, H, scale, shave, params, result, ws, ws_bytes, s);
+                });
+}
+
 Event ConfigBasedDataPipeline::backpropagate(LayerAllocationPool& l1, LayerAllocationPool& l2,
                                              LayerAllocationPool& l3, size_t w, size_t h, size_t n,
                                              Event* ev) {

@@ -170,6 +170,26 @@ class ConfigBasedDataPipeline : public DataPipeline {
    * small for one tile): nothing is kept.  Every call of a run takes the same
    * `tile`. */
   TrainingGrid make_training_planes(ImageData& full, unsigned scale, size_t tile, size_t stride);
+  /** make_training_pairs for the luma of a Y'CbCr frame that is already on the
+   * device: one srcnn_make_pairs_frame call (only frame.y is
+   * read), counted as kernel 'srcnn_make_pairs_frame'. */
+  size_t make_training_pairs(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& frame, unsigned W, unsigned H,
+                             unsigned scale, size_t tile, size_t stride, std::vector<SampleAllocationPool>& out);
+  /** make_training_planes for such a frame: the same one call into a workspace
+   * that stays resident; its X and T planes are registered as one
+   * srcnn_plane_pair (the tiles the call also cuts are dropped). */
+  TrainingGrid make_training_planes(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& frame, unsigned W,
+                                    unsigned H, unsigned scale, size_t tile, size_t stride);
+  /** "How many dB over bicubic?" for a Y'CbCr frame that is already on the
+   * device: one srcnn_evaluate_frame call on the pipeline's flat parameters;
+   * the 16 doubles go to `result` (device) through the caller's workspace
+   * (evaluate_frame_workspace_bytes; 0 where the call would be invalid).  Only
+   * enqueues, on `stream`, or, with no stream, on the context's, where the
+   * call is counted and timed. */
+  void evaluate_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& truth, unsigned W, unsigned H,
+                      unsigned scale, unsigned shave, double* result, void* ws, size_t ws_bytes,
+                      srcnn_stream_t stream = nullptr);
+  size_t evaluate_frame_workspace_bytes(const srcnn_yuv_format& fmt, unsigned W, unsigned H, unsigned scale);
   /** the registered plane pairs to the device; call after the last make_training_planes */
   void upload_plane_table();
   size_t plane_count() const { return _plane_table.size(); }
@@ -271,6 +291,8 @@ class ConfigBasedDataPipeline : public DataPipeline {
   Kernel* _upscale_frame_to_kernel = nullptr;
   Kernel* _make_pairs_kernel = nullptr;
   Kernel* _planes_kernel = nullptr;
+  Kernel* _make_pairs_frame_kernel = nullptr;
+  Kernel* _evaluate_frame_kernel = nullptr;
 
   // resident planes of make_training_planes and the records of the current epoch
   std::vector<srcnn_plane_pair> _plane_table;

@@ -426,6 +426,20 @@ QualityReport DataPipeline::quality(ImageData& img, ImageData& ref, unsigned sha
   return q;
 }
 
+void DataPipeline::downscale_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src,
+                                   const srcnn_yuv_frame& dst, unsigned W, unsigned H, unsigned scale,
+                                   srcnn_stream_t stream) {
+  check_initialized(LOAD_KERNEL_LUMA);
+  if (stream) {
+    check(srcnn_downscale_frame(&fmt, &src, &dst, W, H, scale, stream), "downscale_frame");
+    return;
+  }
+  if (!_downscale_frame_kernel)
+    _downscale_frame_kernel = _context->create_kernel(srcnn::KernelKind::Luma, "srcnn_downscale_frame");
+  srcnn::Context::Launch l(*_context, *_downscale_frame_kernel);
+  check(srcnn_downscale_frame(&fmt, &src, &dst, W, H, scale, _context->stream()), "downscale_frame");
+}
+
 void DataPipeline::quality_frame(const srcnn_yuv_format& fmt_a, const srcnn_yuv_frame& a,
                                  const srcnn_yuv_format& fmt_b, const srcnn_yuv_frame& b, unsigned w, unsigned h,
                                  unsigned shave, double* result, void* ws, size_t ws_bytes, srcnn_stream_t stream) {

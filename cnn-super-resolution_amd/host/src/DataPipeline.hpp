@@ -132,6 +132,14 @@ class DataPipeline {
    * (w / scale) x (h / scale), alpha 255 (srcnn_downscale_rgba). */
   void downscale(ImageData& img, unsigned scale, ImageData& out);
 
+  /** Extension, Y'CbCr frames: the device frame `src` of W x H
+   * luma samples downscaled by `scale` (1..4) into `dst`, (W / scale) x
+   * (H / scale) in the same format: one srcnn_downscale_frame call.  Only
+   * enqueues, on `stream`, or, with no stream, on the context's, where the
+   * call is counted and timed. */
+  void downscale_frame(const srcnn_yuv_format& fmt, const srcnn_yuv_frame& src, const srcnn_yuv_frame& dst,
+                       unsigned W, unsigned H, unsigned scale, srcnn_stream_t stream = nullptr);
+
   /** Extension: PSNR and SSIM of `img` against `ref` (equal sizes, any of 1,
    * 3 or 4 channels each), measured on the device on the full-range luma
    * with `shave` pixels dropped per side (srcnn_quality).  Blocking. */
@@ -251,6 +259,7 @@ class DataPipeline {
   Kernel* _gather_batch_kernel = nullptr;
   Kernel* _quality_kernel = nullptr;
   Kernel* _quality_frame_kernel = nullptr;
+  Kernel* _downscale_frame_kernel = nullptr;
   Kernel* _squared_error_kernel = nullptr;
   Kernel* _sum_kernel = nullptr;
   Kernel* _sum_squared_kernel = nullptr;

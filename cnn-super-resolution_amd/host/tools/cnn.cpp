@@ -6,7 +6,7 @@
 //       [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]
 //       [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]
 //       [--device-batches] [--augment] [--random-origins] [--frames N]
-//       [--range full|limited] [--slots N] [--size WxH]
+//       [--range full|limited] [--slots N] [--size WxH] [--frame-step N]
 //
 // forward:  IN is an image (JPEG / PNG / PNM) that is already scaled, OUT the
 //           result image of the same size (its outermost total_padding / 2
@@ -41,6 +41,10 @@
 //           size (RGB), resampled on the device by the inverse of the upscale
 //           mode's bicubic (srcnn_downscale_rgba): the tool that makes an input
 //           for `cnn upscale`.  Needs no CONFIG.
+//           A Y4M video is streamed frame by frame through
+//           srcnn_downscale_frame: OUT is a Y4M of W/S x H/S with the same F,
+//           I, A, C and XCOLORRANGE tokens, at every depth upscale accepts;
+//           --frames N stops after N frames.
 //           --ref TRUTH.y4m (Y4M input only): TRUTH has the output's size,
 //           subsampling and depth; each of its frames is uploaded into the
 //           slot and the upscaled frame is measured against it where it lies,
@@ -65,6 +69,11 @@
 //           (srcnn_evaluate): one line per image with the net's and bicubic's
 //           PSNR and SSIM and the gain in dB, then the means.  --shave defaults
 //           to S (the literature's rule); -o writes the numbers as JSON.
+//           A Y4M video is evaluated frame by frame (srcnn_evaluate_frame): one
+//           line per frame for the net and one for bicubic as `cnn quality`
+//           prints them, the gain in dB, then both streams' numbers; the JSON
+//           holds the two reports in `cnn quality`'s shape under "net" and
+//           "bicubic".  --frames N stops after N frames.
 // train:    IN is a directory of <name>_large.<ext> / <name>_small.<ext> pairs
 //           (ground truth / degraded input, tools/make_samples.py makes
 //           them), OUT the parameters.json written at the end.
@@ -72,7 +81,10 @@
 //           images; each is cut on the device into --tile x --tile pairs at
 //           --stride (defaults 33 and 14, the paper's sub-image size and
 //           stride), the input tiles degraded by exactly what `cnn upscale
-//           --scale S` applies at inference (srcnn_make_pairs).
+//           --scale S` applies at inference (srcnn_make_pairs).  A Y4M video
+//           in the directory contributes the luma of every --frame-step'th
+//           frame, cut by srcnn_make_pairs_frame on its code values and range;
+//           the closing line counts frames as images.
 //           --device-batches keeps each image's two luma planes on the device
 //           instead of its tiles; every chunk of every epoch is then gathered
 //           from them by a list of {plane, origin, orientation} records in one
@@ -142,6 +154,8 @@ struct Args {
   std::string ref;       // quality: --ref; upscale, Y4M: the truth to measure against
   size_t frames = 0;     // upscale, quality, Y4M: --frames (0: all)
   bool frames_set = false;
+  size_t frame_step = 1;  // train --from-images, Y4M: every Nth frame
+  bool frame_step_set = false;
   int range = -1;        // upscale, Y4M: --range (-1: the header's, 0 limited, 1 full)
   unsigned slots = 2;    // upscale, Y4M: --slots
   bool slots_set = false;
@@ -167,7 +181,7 @@ void usage() {
          "           [--devices N] [--validation-percent P] [--mini-batches M] [--save-momentum]\n"
          "           [--from-images] [--tile N] [--stride N] [--ref REF] [--shave N]\n"
          "           [--device-batches] [--augment] [--random-origins] [--frames N]\n"
-         "           [--range full|limited] [--slots N] [--size WxH]\n\n"
+         "           [--range full|limited] [--slots N] [--size WxH] [--frame-step N]\n\n"
          "  -h, --help            print this help\n"
          "  --version             library ABI, HIP runtime and RCCL the binary runs on\n"
          "  train                 train mode\n"
@@ -181,6 +195,9 @@ void usage() {
          "  downscale             downscale mode: IN is a full-size image, OUT the image of\n"
          "                        1 / --scale the size (the inverse of the upscale mode's\n"
          "                        bicubic, on the device; -c is not needed)\n"
+         "                        A Y4M video is streamed frame by frame, luma and chroma\n"
+         "                        planes alike on their code values; OUT is a Y4M of\n"
+         "                        1 / --scale the size, same depth and tokens\n"
          "  quality               quality mode: PSNR, SSIM and MSE of the image IN against\n"
          "                        --ref REF (equal sizes), measured on the device on the\n"
          "                        full-range luma; -c and -o are not needed\n"
@@ -193,6 +210,9 @@ void usage() {
          "                        net and by plain bicubic, and both are measured against\n"
          "                        it: PSNR, SSIM and the gain in dB per image and their\n"
          "                        means; -o writes them as JSON\n"
+         "                        A Y4M video is evaluated frame by frame on its code\n"
+         "                        values: the net's and bicubic's PSNR of Y, U, V and all,\n"
+         "                        SSIM of Y and the gain in dB, then the stream's numbers\n"
          "  dry                   do not store the result\n"
          "  profile               print kernel execution times\n"
          "  -c, --config CONFIG   CNN configuration (config.json)\n"
@@ -206,7 +226,10 @@ void usage() {
          "  --size WxH            upscale: the output size instead of --scale, each axis\n"
          "                        within 1x .. 4x of the input's (any ratio, also a\n"
          "                        different one per axis)\n"
-         "  --frames N            upscale, quality, Y4M: stop after N frames\n"
+         "  --frames N            upscale, downscale, quality, evaluate, Y4M: stop after N\n"
+         "                        frames\n"
+         "  --frame-step N        train --from-images: of a Y4M video in the directory take\n"
+         "                        every Nth frame (default 1)\n"
          "  --range full|limited  upscale, Y4M: the luma range (default: the header's\n"
          "                        XCOLORRANGE, else limited)\n"
          "  --slots N             upscale, Y4M: frames in flight, 1 or 2 (default 2)\n"
@@ -219,7 +242,8 @@ void usage() {
          "                        for evaluate and upscale --scale, 0 for upscale --size)\n"
          "  --from-images         train: IN is a directory of full-size images; the sample\n"
          "                        pairs are cut on the device, the inputs degraded by\n"
-         "                        --scale as the upscale mode resamples\n"
+         "                        --scale as the upscale mode resamples; a Y4M video in the\n"
+         "                        directory contributes its frames' luma\n"
          "  --tile N              --from-images: sample size (default 33)\n"
          "  --stride N            --from-images: step between samples (default 14)\n"
          "  --device-batches      --from-images: keep the images' luma planes on the device\n"
@@ -288,6 +312,19 @@ bool parse(int argc, char** argv, Args& a) {
         throw std::runtime_error("--frames must be a positive integer");
       a.frames = n;
       a.frames_set = true;
+    }
+    else if (s == "--frame-step") {
+      const std::string v = value("--frame-step");
+      size_t n = 0, used = 0;
+      try {
+        n = std::stoul(v, &used);
+      } catch (const std::exception&) {
+        used = 0;
+      }
+      if (used != v.size() || v.empty() || v[0] == '-' || n == 0)
+        throw std::runtime_error("--frame-step must be a positive integer");
+      a.frame_step = n;
+      a.frame_step_set = true;
     }
     else if (s == "--range") {
       const std::string v = value("--range");
@@ -373,8 +410,9 @@ bool parse(int argc, char** argv, Args& a) {
   if (a.size_set && !a.upscale) throw std::runtime_error("--size needs the upscale mode");
   if ((a.range >= 0 || a.slots_set) && !a.upscale)
     throw std::runtime_error("--range and --slots need the upscale mode");
-  if (a.frames_set && !a.upscale && !a.quality)
-    throw std::runtime_error("--frames needs the upscale mode or the quality mode");
+  if (a.frames_set && !a.upscale && !a.quality && !a.downscale && !a.evaluate)
+    throw std::runtime_error("--frames needs the upscale, downscale, quality or evaluate mode");
+  if (a.frame_step_set && !a.from_images) throw std::runtime_error("--frame-step needs train --from-images");
   // (upscale --ref measures a Y4M stream's frames; an image input has nothing to measure per frame)
   if (!a.ref.empty() && !a.quality && !(a.upscale && is_y4m(a.in)))
     throw std::runtime_error("--ref needs the quality mode, or the upscale mode with a Y4M input");
@@ -554,9 +592,10 @@ class StreamQuality {
     const size_t ws = srcnn_quality_frame_workspace_bytes(hd.w, hd.h, hd.cx, hd.cy, shave);
     srcnn::require(ws > 0, std::string("quality: ") + srcnn_last_error());
   }
-  void add(const double* r) {
+  /** label: what is measured, where one stream has several reports (" net") */
+  void add(const double* r, const char* label = "") {
     const FrameQualityReport q{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
-    std::cout << "frame " << _frames.size() << ": psnr y " << num(q.psnr_y) << " dB u " << num(q.psnr_u) << " dB v "
+    std::cout << "frame " << _frames.size() << label << ": psnr y " << num(q.psnr_y) << " dB u " << num(q.psnr_u) << " dB v "
               << num(q.psnr_v) << " dB all " << num(q.psnr_all) << " dB ssim " << num(q.ssim_y) << std::endl;
     _frames.push_back(q);
   }
@@ -578,19 +617,27 @@ class StreamQuality {
     return t;
   }
   double psnr(double mse) const { return mse == 0 ? double(INFINITY) : 10.0 * std::log10(_peak2 / mse); }
-  void print_stream() const {
+  void print_stream(const char* label = "") const {
     if (_frames.empty()) return;
     const Totals t = totals();
-    std::cout << "stream, " << _frames.size() << " frames: mse y " << num(t.mse_y) << " u " << num(t.mse_u) << " v "
+    std::cout << "stream" << label << ", " << _frames.size() << " frames: mse y " << num(t.mse_y) << " u " << num(t.mse_u) << " v "
               << num(t.mse_v) << " all " << num(t.mse_all) << std::endl
-              << "stream, " << _frames.size() << " frames: psnr y " << num(psnr(t.mse_y)) << " dB u "
+              << "stream" << label << ", " << _frames.size() << " frames: psnr y " << num(psnr(t.mse_y)) << " dB u "
               << num(psnr(t.mse_u)) << " dB v " << num(psnr(t.mse_v)) << " dB all " << num(psnr(t.mse_all))
               << " dB ssim " << num(t.ssim) << std::endl
-              << "lowest psnr y: " << num(t.min_psnr_y) << " dB at frame " << t.min_frame << std::endl;
+              << "lowest psnr y" << label << ": " << num(t.min_psnr_y) << " dB at frame " << t.min_frame << std::endl;
   }
+  double psnr_y(size_t frame) const { return _frames[frame].psnr_y; }
   void write_json(const std::string& path) const {
     std::ofstream out(path);
     if (!out) throw srcnn::IOException("cannot write report '" + path + "'");
+    write_json(out);
+    out.flush();
+    if (!out) throw srcnn::IOException("cannot write report '" + path + "'");
+    std::cout << "Saving report to: '" << path << "'" << std::endl;
+  }
+  /** the report as one JSON object */
+  void write_json(std::ostream& out) const {
     out << "{\n  \"width\": " << _hd.w << ", \"height\": " << _hd.h << ", \"bits\": " << _hd.bits
         << ", \"chroma\": \"" << _hd.chroma << "\", \"shave\": " << _shave << ",\n  \"frames\": [\n";
     for (size_t i = 0; i < _frames.size(); ++i) {
@@ -611,9 +658,6 @@ class StreamQuality {
           << ", \"ssim_y\": " << json_num(t.ssim) << ", \"min_psnr_y\": " << json_num(t.min_psnr_y)
           << ", \"min_psnr_y_frame\": " << t.min_frame;
     out << "}\n}\n";
-    out.flush();
-    if (!out) throw srcnn::IOException("cannot write report '" + path + "'");
-    std::cout << "Saving report to: '" << path << "'" << std::endl;
   }
 
  private:
@@ -776,8 +820,98 @@ int upscale(ConfigBasedDataPipeline& p, const Args& a) {
   return 0;
 }
 
-/** `cnn downscale`: the full-size image through srcnn_downscale_rgba */
+/** Device and pinned host buffers of one streaming run, released when it ends,
+ * whatever ended it. */
+struct Buffers {
+  std::vector<void*> dev, host;
+  Buffers() = default;
+  Buffers(const Buffers&) = delete;
+  Buffers& operator=(const Buffers&) = delete;
+  ~Buffers() {
+    srcnn_device_sync();
+    for (void* d : dev) srcnn_free(d);
+    for (void* h : host) srcnn_host_free(h);
+  }
+  void* device(size_t bytes) {
+    void* d = nullptr;
+    srcnn::check(srcnn_malloc(&d, bytes), "malloc");
+    dev.push_back(d);
+    return d;
+  }
+  void* pinned(size_t bytes) {
+    void* h = nullptr;
+    srcnn::check(srcnn_host_alloc(&h, bytes), "host_alloc");
+    host.push_back(h);
+    return h;
+  }
+};
+
+/** a Y4M stream's frame format: planes, the values in the low bits of their words */
+srcnn_yuv_format format_of(const srcnn::y4m::Header& hd) {
+  return srcnn_yuv_format{hd.bits, 0, SRCNN_YUV_PLANAR, hd.cx, hd.cy, hd.full_range ? SRCNN_YUV_FULL : SRCNN_YUV_LIMITED};
+}
+
+/** `cnn downscale` on a Y4M stream: every frame through srcnn_downscale_frame,
+ * one at a time on the context's stream */
+int downscale_y4m(DataPipeline& p, const Args& a, std::istream& in) {
+  namespace y4m = srcnn::y4m;
+  const y4m::Header hd = y4m::read_header(in);
+  srcnn::require(hd.w >= a.scale && hd.h >= a.scale,
+                 "frame " + std::to_string(hd.w) + "x" + std::to_string(hd.h) + " is smaller than the scale");
+  y4m::Header ohd = hd;  // F, I, A, C and XCOLORRANGE as they are
+  ohd.w = hd.w / a.scale;
+  ohd.h = hd.h / a.scale;
+  const srcnn_yuv_format fmt = format_of(hd);
+  std::cout << "Y4M video: " << hd.w << "x" << hd.h << " C" << hd.chroma << " -> " << ohd.w << "x" << ohd.h << std::endl;
+  std::ofstream out;
+  const bool store = !a.dry && !a.out.empty();
+  if (store) {
+    out.open(a.out, std::ios::binary);
+    if (!out) throw srcnn::IOException("cannot open '" + a.out + "' for writing");
+    y4m::write_header(out, ohd);
+  }
+  Buffers b;
+  unsigned char* host_in = static_cast<unsigned char*>(b.pinned(hd.frame_bytes()));
+  unsigned char* host_out = static_cast<unsigned char*>(b.pinned(ohd.frame_bytes()));
+  const srcnn_yuv_frame src = FrameSlot::planes(b.device(hd.frame_bytes()), hd);
+  const srcnn_yuv_frame dst = FrameSlot::planes(b.device(ohd.frame_bytes()), ohd);
+  srcnn_stream_t stream = p.context()->stream();
+  int rc = 0;
+  size_t k = 0;
+  for (; !a.frames_set || k < a.frames; ++k) {
+    try {
+      if (!y4m::read_frame(in, hd, host_in)) break;
+    } catch (const srcnn::IOException& e) {
+      std::cout << "[ERROR] frame " << k << ": " << e.what() << std::endl;
+      rc = 1;
+      break;
+    }
+    srcnn::check(srcnn_memcpy_h2d(src.y, host_in, hd.frame_bytes(), stream), "memcpy_h2d");
+    p.downscale_frame(fmt, src, dst, hd.w, hd.h, a.scale);
+    srcnn::check(srcnn_memcpy_d2h(host_out, dst.y, ohd.frame_bytes(), stream), "memcpy_d2h");
+    if (store) y4m::write_frame(out, ohd, host_out);
+  }
+  if (store) {
+    out.flush();
+    if (!out) throw srcnn::IOException("cannot write '" + a.out + "'");
+  }
+  std::cout << "Frames: " << k << (store ? ", saved to '" + a.out + "'" : std::string()) << std::endl;
+  p.context()->block();
+  return rc;
+}
+
+/** `cnn downscale`: the full-size image through srcnn_downscale_rgba, or a
+ * Y4M video through srcnn_downscale_frame frame by frame */
 int downscale(DataPipeline& p, const Args& a) {
+  {
+    std::ifstream in(a.in, std::ios::binary);
+    char magic[9] = {};
+    if (in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0) {
+      in.seekg(0);
+      return downscale_y4m(p, a, in);
+    }
+  }
+  if (a.frames_set) throw std::runtime_error("--frames needs a Y4M input");
   ImageData img, small;
   srcnn::image::load(a.in, img, 4);
   srcnn::require(img.w >= int(a.scale) && img.h >= int(a.scale),
@@ -912,9 +1046,83 @@ int quality(DataPipeline& p, const Args& a) {
   return 0;
 }
 
+/** `cnn evaluate` on a Y4M stream: every frame through srcnn_evaluate_frame, one
+ * at a time on the context's stream; the net's and bicubic's numbers as two
+ * stream reports of `cnn quality`'s shape */
+int evaluate_y4m(ConfigBasedDataPipeline& p, const Args& a, std::istream& in) {
+  namespace y4m = srcnn::y4m;
+  const y4m::Header hd = y4m::read_header(in);
+  srcnn::require(hd.w >= a.scale && hd.h >= a.scale,
+                 "frame " + std::to_string(hd.w) + "x" + std::to_string(hd.h) + " is smaller than the scale");
+  y4m::Header mhd = hd;  // what is measured: the truth's top-left s*(W/s) x s*(H/s)
+  mhd.w = hd.w / a.scale * a.scale;
+  mhd.h = hd.h / a.scale * a.scale;
+  const srcnn_yuv_format fmt = format_of(hd);
+  StreamQuality::check(mhd, a.shave);
+  const size_t ws_bytes = p.evaluate_frame_workspace_bytes(fmt, hd.w, hd.h, a.scale);
+  srcnn::require(ws_bytes > 0, std::string("evaluate: ") + srcnn_last_error());
+  std::cout << "Y4M video: " << hd.w << "x" << hd.h << " C" << hd.chroma << ", " << hd.bits << " bits, scale " << a.scale
+            << ", measured on " << mhd.w << "x" << mhd.h << ", shave " << a.shave << std::endl;
+  StreamQuality net(mhd, a.shave), bic(mhd, a.shave);
+  Buffers b;
+  unsigned char* host = static_cast<unsigned char*>(b.pinned(hd.frame_bytes()));
+  double* host_res = static_cast<double*>(b.pinned(16 * sizeof(double)));
+  const srcnn_yuv_frame truth = FrameSlot::planes(b.device(hd.frame_bytes()), hd);
+  void* ws = b.device(ws_bytes);
+  double* dev_res = static_cast<double*>(b.device(16 * sizeof(double)));
+  srcnn_stream_t stream = p.context()->stream();
+  int rc = 0;
+  for (size_t k = 0; !a.frames_set || k < a.frames; ++k) {
+    try {
+      if (!y4m::read_frame(in, hd, host)) break;
+    } catch (const srcnn::IOException& e) {
+      std::cout << "[ERROR] frame " << k << ": " << e.what() << std::endl;
+      rc = 1;
+      break;
+    }
+    srcnn::check(srcnn_memcpy_h2d(truth.y, host, hd.frame_bytes(), stream), "memcpy_h2d");
+    p.evaluate_frame(fmt, truth, hd.w, hd.h, a.scale, a.shave, dev_res, ws, ws_bytes);
+    srcnn::check(srcnn_memcpy_d2h(host_res, dev_res, 16 * sizeof(double), stream), "memcpy_d2h");
+    net.add(host_res, " net");
+    bic.add(host_res + 8, " bicubic");
+    std::cout << "frame " << k << " gain: " << num(host_res[1] - host_res[9]) << " dB" << std::endl;
+  }
+  if (net.count() == 0) throw std::runtime_error("no frame to evaluate in '" + a.in + "'");
+  net.print_stream(" net");
+  bic.print_stream(" bicubic");
+  const double gain = net.psnr(net.totals().mse_y) - bic.psnr(bic.totals().mse_y);
+  std::cout << "stream gain: " << num(gain) << " dB" << std::endl;
+  if (!a.dry && !a.out.empty()) {
+    std::ofstream out(a.out);
+    if (!out) throw srcnn::IOException("cannot write report '" + a.out + "'");
+    out << "{\n\"scale\": " << a.scale << ",\n\"net\": ";
+    net.write_json(out);
+    out << ",\n\"bicubic\": ";
+    bic.write_json(out);
+    out << ",\n\"gain_db\": [";
+    for (size_t i = 0; i < net.count(); ++i) out << (i ? ", " : "") << json_num(net.psnr_y(i) - bic.psnr_y(i));
+    out << "],\n\"stream_gain_db\": " << json_num(gain) << "\n}\n";
+    out.flush();
+    if (!out) throw srcnn::IOException("cannot write report '" + a.out + "'");
+    std::cout << "Saving report to: '" << a.out << "'" << std::endl;
+  }
+  p.context()->block();
+  return rc;
+}
+
 /** `cnn evaluate`: IN, or every file of the directory IN that decodes, in name
- * order, through srcnn_evaluate */
+ * order, through srcnn_evaluate; a Y4M video through srcnn_evaluate_frame frame
+ * by frame */
 int evaluate(ConfigBasedDataPipeline& p, const Args& a) {
+  {
+    std::ifstream in(a.in, std::ios::binary);
+    char magic[9] = {};
+    if (in.read(magic, 9) && std::memcmp(magic, "YUV4MPEG2", 9) == 0) {
+      in.seekg(0);
+      return evaluate_y4m(p, a, in);
+    }
+  }
+  if (a.frames_set) throw std::runtime_error("--frames needs a Y4M input");
   std::vector<std::string> names;  // relative to `base`
   std::string base;
   if (DIR* d = opendir(a.in.c_str())) {
@@ -1014,7 +1222,45 @@ void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
   closedir(d);
   std::sort(names.begin(), names.end());
   size_t images = 0;
+  // one sample per tile of the grid g, as records or as the tiles already appended
+  auto record = [&](const ConfigBasedDataPipeline::TrainingGrid& g) {
+    for (size_t i = 0; i < g.count; ++i) {
+      grid.push_back({uint32_t(g.plane), uint32_t(i % g.nx * a.stride), uint32_t(i / g.nx * a.stride), 0});
+      extent.push_back({uint32_t(g.w), uint32_t(g.h)});
+    }
+  };
   for (auto& f : names) {
+    if (is_y4m(a.in + "/" + f)) {
+      // a Y4M video: the luma of every --frame-step'th frame, cut on its code values
+      namespace y4m = srcnn::y4m;
+      std::ifstream in(a.in + "/" + f, std::ios::binary);
+      const y4m::Header hd = y4m::read_header(in);
+      const srcnn_yuv_format fmt = format_of(hd);
+      Buffers b;
+      unsigned char* host = static_cast<unsigned char*>(b.pinned(hd.frame_bytes()));
+      const srcnn_yuv_frame frame{static_cast<uint8_t*>(b.device(hd.luma_bytes())), nullptr, nullptr,
+                                  uint32_t(hd.w * hd.sample_bytes()), 0};
+      for (size_t k = 0; y4m::read_frame(in, hd, host); ++k) {
+        if (k % a.frame_step) continue;
+        srcnn::check(srcnn_memcpy_h2d(frame.y, host, hd.luma_bytes(), p.context()->stream()), "memcpy_h2d");
+        size_t n;
+        if (a.device_batches) {
+          const auto g = p.make_training_planes(fmt, frame, hd.w, hd.h, a.scale, a.tile, a.stride);
+          n = g.count;
+          record(g);
+        } else {
+          n = p.make_training_pairs(fmt, frame, hd.w, hd.h, a.scale, a.tile, a.stride, samples);
+        }
+        if (n == 0) {
+          if (lead)
+            std::cout << "'" << f << "' (" << hd.w << "x" << hd.h << ") is too small for one " << a.tile << "x"
+                      << a.tile << " tile at scale " << a.scale << ". Skipping video" << std::endl;
+          break;
+        }
+        ++images;
+      }
+      continue;
+    }
     ImageData img;
     try {
       srcnn::image::load(a.in + "/" + f, img, 4);
@@ -1026,10 +1272,7 @@ void pairs_from_images(ConfigBasedDataPipeline& p, const Args& a, bool lead,
     if (a.device_batches) {
       const auto g = p.make_training_planes(img, a.scale, a.tile, a.stride);
       n = g.count;
-      for (size_t i = 0; i < n; ++i) {
-        grid.push_back({uint32_t(g.plane), uint32_t(i % g.nx * a.stride), uint32_t(i / g.nx * a.stride), 0});
-        extent.push_back({uint32_t(g.w), uint32_t(g.h)});
-      }
+      record(g);
     } else {
       n = p.make_training_pairs(img, a.scale, a.tile, a.stride, samples);
     }

@@ -129,6 +129,12 @@ SIGNATURES = {
     "srcnn_quality": (_I, [_P, _I, _U, _P, _I, _U, _U, _U, _U, _P, _P, _S, _P]),
     "srcnn_quality_frame_workspace_bytes": (_S, [_U, _U, _U, _U, _U]),
     "srcnn_quality_frame": (_I, [_MP, _FP, _MP, _FP, _U, _U, _U, _P, _P, _S, _P]),
+    "srcnn_downscale_planes": (_I, [_P, _P, _U, _U, _U, _P, _P, _U, _U, _U, _U, _U, _U, _U, _P]),
+    "srcnn_downscale_frame": (_I, [_MP, _FP, _FP, _U, _U, _U, _P]),
+    "srcnn_make_pairs_frame_workspace_bytes": (_S, [_MP, _U, _U, _U]),
+    "srcnn_make_pairs_frame": (_I, [_MP, _FP, _U, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
+    "srcnn_evaluate_frame_workspace_bytes": (_S, [_NP, _MP, _U, _U, _U]),
+    "srcnn_evaluate_frame": (_I, [_NP, _MP, _FP, _U, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_upscale_workspace_bytes": (_S, [_NP, _U, _U, _U]),
     "srcnn_upscale": (_I, [_NP, _P, _U, _U, _U, _P, _P, _P, _S, _P]),
     "srcnn_upscale_yuv_workspace_bytes": (_S, [_NP, _U, _U, _U]),
@@ -694,6 +700,53 @@ def quality_frame(fmt_a, a, fmt_b, b, w, h, shave, result, ws, ws_bytes, s=None)
     ref = lambda x: ctypes.byref(x) if x is not None else None
     _call("srcnn_quality_frame", ref(fmt_a), ref(a), ref(fmt_b), ref(b), w, h, shave, ptr(result), ptr(ws),
           ws_bytes, s)
+
+
+def _ref(x):
+    return ctypes.byref(x) if x is not None else None
+
+
+def downscale_planes(src0, src1, src_pitch, pw, ph, dst0, dst1, dst_pitch, ow, oh, scale, bits, msb, layout, s=None):
+    """A frame's planes [ph][pw] of `bits`-bit samples -> the antialiased
+    bicubic / scale of the code values, [oh][ow] with ow <= ceil(pw / scale),
+    oh likewise, rounded to nearest even and clamped.  YUV_PLANAR: one plane
+    (src1 and dst1 None) or two; YUV_SEMIPLANAR: src0 / dst0 hold (U, V)
+    pairs; pitches in bytes (srcnn_downscale_planes)."""
+    _call("srcnn_downscale_planes", ptr(src0), ptr(src1), src_pitch, pw, ph, ptr(dst0), ptr(dst1), dst_pitch, ow,
+          oh, scale, bits, msb, layout, s)
+
+
+def downscale_frame(fmt, src, dst, W, H, scale, s=None):
+    """One Y'CbCr frame of W x H luma samples (src, a YuvFrame) -> the frame
+    W // scale x H // scale in the same YuvFormat (dst): downscale_planes of
+    the luma, then of the chroma (srcnn_downscale_frame)."""
+    _call("srcnn_downscale_frame", _ref(fmt), _ref(src), _ref(dst), W, H, scale, s)
+
+
+def make_pairs_frame_workspace_bytes(fmt, W, H, scale):
+    return _lib.srcnn_make_pairs_frame_workspace_bytes(_ref(fmt), W, H, scale)
+
+
+def make_pairs_frame(fmt, frame, W, H, scale, tile, stride, X, T, ws, ws_bytes, s=None):
+    """The luma of a Y'CbCr frame -> X, T [count][tile][tile] f32
+    (srcnn_make_pairs_frame): downscale_planes of Y, yuv_upscale_luma16 of the
+    small plane (pad 0) and of Y itself at scale 1, gather_tiles with the mean
+    (X) and without (T).  Only frame.y is read."""
+    _call("srcnn_make_pairs_frame", _ref(fmt), _ref(frame), W, H, scale, tile, stride, ptr(X), ptr(T), ptr(ws),
+          ws_bytes, s)
+
+
+def evaluate_frame_workspace_bytes(net, fmt, W, H, scale):
+    return _lib.srcnn_evaluate_frame_workspace_bytes(_ref(net), _ref(fmt), W, H, scale)
+
+
+def evaluate_frame(net, fmt, truth, W, H, scale, shave, params, result, ws, ws_bytes, s=None):
+    """Full-size truth frame -> result (16 doubles, device): quality_frame's
+    eight values of the net's x scale result, then of plain bicubic's
+    (srcnn_evaluate_frame): downscale_frame, upscale_frame, quality_frame,
+    yuv_upscale_luma16 (pad 0), yuv_compose_luma16, quality_frame."""
+    _call("srcnn_evaluate_frame", _ref(net), _ref(fmt), _ref(truth), W, H, scale, shave, ptr(params), ptr(result),
+          ptr(ws), ws_bytes, s)
 
 
 def upscale_to_workspace_bytes(net, w, h, W, H):

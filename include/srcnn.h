@@ -503,8 +503,8 @@ typedef struct srcnn_net {
 /* Resolve, on the current device, every gfx950 kernel the net-level calls
  * (srcnn_train_fwd_bwd, srcnn_update_all, srcnn_forward, srcnn_upscale,
  * srcnn_upscale_yuv, srcnn_upscale_to, srcnn_upscale_frame_to) launch for this
- * net, and the kernels of srcnn_make_pairs, srcnn_quality and
- * srcnn_quality_frame.
+ * net, and the kernels of srcnn_make_pairs, srcnn_quality,
+ * srcnn_quality_frame and srcnn_downscale_planes.
  * No kernel runs.  The HIP runtime otherwise sets a kernel up lazily at its
  * first launch; resolving them beforehand keeps that out of the first step
  * (the reference builds its kernels up front too: src/ConfigBasedDataPipeline
@@ -536,7 +536,8 @@ SRCNN_API size_t srcnn_net_param_count(const srcnn_net* net);
  *     planes, not the pitch gaps between them; srcnn_make_pairs: count*tile*tile floats of X and of
  *     T each; srcnn_gather_batch, which takes no workspace: n*tw*th floats of
  *     X and of T each and the n of means; srcnn_quality / srcnn_evaluate /
- *     srcnn_quality_frame: the 3 / 6 / 8 doubles of result);
+ *     srcnn_quality_frame / srcnn_evaluate_frame: the 3 / 6 / 8 / 16 doubles of
+ *     result; srcnn_make_pairs_frame as srcnn_make_pairs);
  *   - buffers the call only reads (X, T, params) are not written, and nothing
  *     outside their extent reaches a result.
  * The results are bit-identical whatever `ws` held before and whatever lies
@@ -732,6 +733,99 @@ SRCNN_API int srcnn_quality_frame(const srcnn_yuv_format* fmt_a, const srcnn_yuv
                                   const srcnn_yuv_format* fmt_b, const srcnn_yuv_frame* b,
                                   uint32_t w, uint32_t h, uint32_t shave, double* result,
                                   void* ws, size_t ws_bytes, srcnn_stream_t stream);
+
+/* The planes of a Y'CbCr frame made smaller, on the device (an MI355X
+ * extension; DESIGN.md 18.1 is the spec): the down direction of
+ * srcnn_upscale_planes.  A plane is [ph][pw] samples of `bits` bits, laid out
+ * and pitched as there; the output is [oh][ow] in the same
+ * layout, 1 <= ow <= ceil(pw/s), 1 <= oh <= ceil(ph/s), s = 1, 2, 3 or 4.  The
+ * resampling is srcnn_downscale_rgba's on the integer code values (for msb = 1
+ * the word >> (16 - bits)): the antialiased Keys bicubic stretched by s at
+ * half-pixel centres, source indices clamped to the plane, separable, fp32,
+ * horizontal pass first, no intermediate rounding; the output sample is
+ * clamp(rintf(v), 0, 2^bits - 1), ties to even as in the video family, not
+ * srcnn_downscale_rgba's floor(v + 0.5).  With s = 1 the output is the source
+ * for every sample within [0, 2^bits - 1].  Down by s, then
+ * srcnn_yuv_upscale_luma16 by s, is shift-free.
+ *
+ * SRCNN_YUV_PLANAR with src1 == dst1 == NULL: one plane (a frame's luma); with
+ * both non-null: two planes in one launch, each as the one-plane call gives
+ * it.  SRCNN_YUV_SEMIPLANAR: src0 / dst0 hold (U, V) pairs, src1 and dst1 must
+ * be NULL; sample for sample the planar call on the de-interleaved planes.
+ * Gaps between rows are never read and never written.  Stream-ordered, one
+ * launch, no workspace; two calls on the same input are bit-identical.
+ *
+ * SRCNN_ERR_INVALID, before any launch: scale outside 1..4; a zero size; ow
+ * or oh beyond its bound; exactly one of src1 / dst1 null; and whatever
+ * srcnn_upscale_planes rejects for pitches, bits, msb, layout, odd addresses
+ * and the 2^31-1 samples of a plane.
+ *
+ * srcnn_downscale_frame: a whole frame of W x H luma samples (W >= s, H >= s)
+ * -> w x h = W/s x H/s (integer division) in the same format, chroma
+ * [ceil(H/cy)][ceil(W/cx)] -> [ceil(h/cy)][ceil(w/cx)] (always within the
+ * bound above).  Two launches, no workspace; byte-identical to
+ * srcnn_downscale_planes(src->y -> dst->y, planar, one plane) and
+ * srcnn_downscale_planes(src->u, src->v -> dst->u, dst->v, fmt->layout).
+ * Chroma is resampled plane-wise with the half-pixel map: exact for
+ * centre-sited chroma; left-sited chroma keeps a residual shift (DESIGN.md
+ * 18.1), uncorrected as in srcnn_upscale_frame.  Errors as the two calls and
+ * as srcnn_upscale_frame for the format and the frames, before any launch. */
+SRCNN_API int srcnn_downscale_planes(const void* src0, const void* src1, uint32_t src_pitch,
+                                     uint32_t pw, uint32_t ph, void* dst0, void* dst1,
+                                     uint32_t dst_pitch, uint32_t ow, uint32_t oh, uint32_t scale,
+                                     uint32_t bits, uint32_t msb, uint32_t layout,
+                                     srcnn_stream_t stream);
+SRCNN_API int srcnn_downscale_frame(const srcnn_yuv_format* fmt, const srcnn_yuv_frame* src,
+                                    const srcnn_yuv_frame* dst, uint32_t W, uint32_t H,
+                                    uint32_t scale, srcnn_stream_t stream);
+
+/* srcnn_make_pairs for the luma of a Y'CbCr frame: X and T [count][tile][tile]
+ * with the grid and count of srcnn_make_pairs_count.  Byte-identical to
+ *   srcnn_downscale_planes(frame->y -> small [h][w], rows w samples apart)
+ *   srcnn_yuv_upscale_luma16(small, w, h, s, pad = 0, range) -> X plane [Hc][Wc]
+ *   srcnn_yuv_upscale_luma16(frame->y, W, H, 1, pad = 0, range) -> T plane [H][W]
+ *   srcnn_gather_tiles(X plane, sub_mean = 1), srcnn_gather_tiles(T plane, 0)
+ * so that limited-range and deep material is trained on as inference sees it.
+ * Only the Y plane is read: frame->u and frame->v may be NULL and pitch_c is
+ * ignored; fmt is validated whole.  `ws` holds the small plane and the two
+ * luma planes (each 256-byte aligned) under the memory contract at
+ * srcnn_train_workspace_bytes; the X and T planes are what a srcnn_plane_pair
+ * wants.  Stream-ordered, five launches, no allocation.  The workspace query
+ * returns 0 where the call would be invalid; errors as the calls it makes and
+ * as srcnn_make_pairs, before any launch, SRCNN_ERR_WORKSPACE for a workspace
+ * that is too small. */
+SRCNN_API size_t srcnn_make_pairs_frame_workspace_bytes(const srcnn_yuv_format* fmt, uint32_t W,
+                                                        uint32_t H, uint32_t scale);
+SRCNN_API int srcnn_make_pairs_frame(const srcnn_yuv_format* fmt, const srcnn_yuv_frame* frame,
+                                     uint32_t W, uint32_t H, uint32_t scale, uint32_t tile,
+                                     uint32_t stride, float* X, float* T, void* ws,
+                                     size_t ws_bytes, srcnn_stream_t stream);
+
+/* srcnn_evaluate for a Y'CbCr frame: the full-size truth goes in, result
+ * (device, 16 doubles) = the net's eight srcnn_quality_frame values, then
+ * plain bicubic's eight.  With w = W/s, h = H/s, Wc = s*w, Hc = s*h it is result
+ * for result bit-identical to
+ *   srcnn_downscale_frame(truth -> small)
+ *   srcnn_upscale_frame(net, small -> out)
+ *   srcnn_quality_frame(out; truth with its own pitches; Wc, Hc, shave) -> result[0..7]
+ *   srcnn_yuv_upscale_luma16(small y, pad = 0) -> plane [Hc][Wc]
+ *   srcnn_yuv_compose_luma16(plane -> out's y)
+ *   srcnn_quality_frame(as above)                                      -> result[8..15]
+ * The chroma planes are the same in both halves, so their numbers coincide.
+ * `ws` holds the small frame, the output frame, the luma plane and the two
+ * calls' workspaces (each 256-byte aligned) under the memory contract at
+ * srcnn_train_workspace_bytes.  Stream-ordered, no host synchronisation, no
+ * allocation.  Errors as the calls it makes, before any launch; result and ws
+ * 8-byte aligned; SRCNN_ERR_WORKSPACE for a workspace that is too small; the
+ * query returns 0 where the call would be invalid. */
+SRCNN_API size_t srcnn_evaluate_frame_workspace_bytes(const srcnn_net* net,
+                                                      const srcnn_yuv_format* fmt, uint32_t W,
+                                                      uint32_t H, uint32_t scale);
+SRCNN_API int srcnn_evaluate_frame(const srcnn_net* net, const srcnn_yuv_format* fmt,
+                                   const srcnn_yuv_frame* truth, uint32_t W, uint32_t H,
+                                   uint32_t scale, uint32_t shave, const float* params,
+                                   double* result, void* ws, size_t ws_bytes,
+                                   srcnn_stream_t stream);
 
 /* "How many dB over bicubic?" in one call: the full-size ground truth rgba
  * [H][W][4] u8 goes in, the net's and plain bicubic's {mse, psnr, ssim} at
